@@ -75,8 +75,10 @@ def compile_one(src, force, extra, obj_dir=OBJ):
     if src == DIGEST_SOURCE:  # rebuilt whenever ANY kernel source moved: the digest it embeds is that of all of them
         digest = source_digest()
         defines, stamp = [f'-DGSSS_SOURCE_DIGEST="{digest}"'], obj + ".digest"
-        if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == digest:
-            return obj, False
+        if not force and os.path.exists(obj) and os.path.exists(stamp):
+            with open(stamp) as f:
+                if f.read() == digest:
+                    return obj, False
     elif not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(path), headers_mtime()):
         return obj, False
     cmd = [hipcc(), *CXXFLAGS, *source_flags(src), *defines, *extra, "-c", path, "-o", obj]
@@ -86,7 +88,8 @@ def compile_one(src, force, extra, obj_dir=OBJ):
     if r.stderr.strip():
         sys.stderr.write(r.stderr)
     if stamp:
-        open(stamp, "w").write(defines[0].split('"')[1])
+        with open(stamp, "w") as f:
+            f.write(defines[0].split('"')[1])
     return obj, True
 
 

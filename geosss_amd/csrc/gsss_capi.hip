@@ -256,31 +256,22 @@ static int transpose(const double *in, double *out, int64_t R, int64_t C, int de
     if (R <= kSkinny || C <= kSkinny) {
         const bool short_rows = R <= C;
         const int64_t longside = short_rows ? C : R;
-        const int64_t grid = (longside + kBlock - 1) / kBlock;
+        const int64_t grid = ceil_div(longside, kBlock);
         if (grid > 0x7FFFFFFFll) {
             set_error("transpose: %lld x %lld exceeds the grid", (long long)R, (long long)C);
             return GSSS_E_UNSUPPORTED;
         }
-        if (short_rows)
-            hipLaunchKernelGGL(transpose_skinny_kernel<true>, dim3((unsigned)grid), dim3(kBlock), 0, st, in, out, R, C);
-        else
-            hipLaunchKernelGGL(transpose_skinny_kernel<false>, dim3((unsigned)grid), dim3(kBlock), 0, st, in, out, R, C);
-        GSSS_HIP_TRY(hipGetLastError());
-        return GSSS_OK;
+        return launch_kernel("transpose", short_rows ? transpose_skinny_kernel<true> : transpose_skinny_kernel<false>, grid, 0, st,
+                             nullptr, in, out, R, C);
     }
-    const int64_t gx = (C + kTile - 1) / kTile, gy = (R + kTile - 1) / kTile;
+    const int64_t gx = ceil_div(C, kTile), gy = ceil_div(R, kTile);
     if (gx * gy > 0x7FFFFFFFll) {
         set_error("transpose: %lld x %lld exceeds the grid", (long long)R, (long long)C);
         return GSSS_E_UNSUPPORTED;
     }
     const bool wide = (R % 2 == 0) && (C % 2 == 0) && (reinterpret_cast<uintptr_t>(in) % 16 == 0) &&
                       (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    if (wide)
-        hipLaunchKernelGGL(transpose_kernel_x2, dim3((unsigned)(gx * gy)), dim3(kBlock), 0, st, in, out, R, C);
-    else
-        hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(gx * gy)), dim3(kBlock), 0, st, in, out, R, C);
-    GSSS_HIP_TRY(hipGetLastError());
-    return GSSS_OK;
+    return launch_kernel("transpose", wide ? transpose_kernel_x2 : transpose_kernel, gx * gy, 0, st, nullptr, in, out, R, C);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -844,11 +835,8 @@ int gsss_sample_sphere(uint64_t seed, uint64_t chain_offset, int64_t n, int32_t 
     if (n == 0) return GSSS_OK;
     DeviceGuard guard(device);
     if (!guard.ok) return GSSS_E_HIP;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(sample_sphere_kernel, dim3((unsigned)grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                       seed, chain_offset, n, (int)d, state_dev);
-    GSSS_HIP_TRY(hipGetLastError());
-    return GSSS_OK;
+    return launch_kernel("sample_sphere", sample_sphere_kernel, ceil_div(n, kBlock), 0, static_cast<hipStream_t>(stream), nullptr,
+                         seed, chain_offset, n, (int)d, state_dev);
 }
 
 int gsss_tangent_s2(const double *x_dev, const uint32_t *w_dev, int64_t n, int32_t table_driven, double *out_dev, int device, void *stream)
@@ -860,11 +848,8 @@ int gsss_tangent_s2(const double *x_dev, const uint32_t *w_dev, int64_t n, int32
     if (n == 0) return GSSS_OK;
     DeviceGuard guard(device);
     if (!guard.ok) return GSSS_E_HIP;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(tangent_s2_kernel, dim3((unsigned)grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), x_dev, w_dev, n,
-                       (int)table_driven, out_dev);
-    GSSS_HIP_TRY(hipGetLastError());
-    return GSSS_OK;
+    return launch_kernel("tangent_s2", tangent_s2_kernel, ceil_div(n, kBlock), 0, static_cast<hipStream_t>(stream), nullptr, x_dev,
+                         w_dev, n, (int)table_driven, out_dev);
 }
 
 int gsss_rows_to_components(const double *in_dev, double *out_dev, int64_t n, int32_t d, int device, void *stream)

@@ -35,12 +35,7 @@ namespace gsss {
 // Measured on MI355X (ms per 10^8 chain-steps at d = 10 / 50): 2 wavefronts 43.7 / 81.1, 3 wavefronts 34.7 / 66.1, 4 wavefronts
 // with 28-38 registers spilled 29.7 / 60.8 -- but then the spill traffic reaches HBM (294 MB of scratch for 25 000 wavefronts
 // do not fit the L2): 3.9 GB / 33 GB per launch against 0.17 / 0.48 GB of algorithmic bytes.  Three it is.
-#ifndef GSSS_CS_WAVES
-#define GSSS_CS_WAVES 3
-#endif
-#ifndef GSSS_CS_WAVES_BIG
-#define GSSS_CS_WAVES_BIG 2
-#endif
+constexpr int kCsWaves = 3, kCsWavesBig = 2;
 // Two or three component quads per lane, <= 10 knots: THREE wavefronts per SIMD with registers in scratch beat two without, while
 // the resident wavefronts' scratch stays in or near the L2 (384 wavefronts per XCD x 64 lanes x the bytes below; 4 MB of L2 per XCD,
 // the memory-side cache behind it).  Measured at 10^5 chains x 1000 steps, ms per launch (profiles/r04_ab_q2_three_waves.log):
@@ -53,37 +48,16 @@ namespace gsss {
 // The 17-knot builds (curves of 11 .. 17 knots) likewise, one and two quads per lane (164 .. 208 B of scratch): 16 knots, 10^5 chains
 // x 1000 steps, <4,1,17> d = 10 34.5 -> 28.3 ms, <4,2,17> d = 24 36.7 -> 30.5, <16,2,17> d = 100 91.8 -> 77.0 (+19 .. 22 %); three quads
 // (<4,3,17>, 300 B) lose 6 % and stay at two.
-#ifndef GSSS_CS_WAVES_K17
-#define GSSS_CS_WAVES_K17 3
-#endif
-#ifndef GSSS_CS_WAVES_Q2
-#define GSSS_CS_WAVES_Q2 3
-#endif
-#ifndef GSSS_CS_WAVES_Q3
-#define GSSS_CS_WAVES_Q3 3
-#endif
-#ifndef GSSS_CS_PARK_FROM_Q
-#define GSSS_CS_PARK_FROM_Q 99  // (A/B builds: component quads per lane from which every 10-knot build parks the tangent in LDS while the tries run)
-#endif
-#ifndef GSSS_CS_PACKED_BELOW
-#define GSSS_CS_PACKED_BELOW 64  // lanes per chain below which the screen evaluates two segments per packed instruction (Curve32<.., PACKED>):
-                                 // every group size (sixteen lanes: packed with preloaded constants lost 1 %, packed without them and
-                                 // with the copy of the loop for full curves gains 1.4 %: d = 200 96.24 -> 94.9 ms)
-#endif
-#ifndef GSSS_CS_PRELOAD_Q
-#define GSSS_CS_PRELOAD_Q 2  // component quads per lane from which the try evaluation reads all segment constants in one go -- in the
-                             // sixteen-lane builds only: the four- and eight-lane ones evaluate segments in pairs and take the copy of the loop
-                             // for full curves instead, which preloading would make spill (round 4: d = 24 27.79 -> 26.58 ms, d = 50 33.90 -> 32.62)
-#endif
-#ifndef GSSS_CS_KNOT_PIPE
-#define GSSS_CS_KNOT_PIPE 1  // knot rows read from LDS one row ahead of their products (more than four components per lane)
-#endif
-#ifndef GSSS_CS_KNOT_PIPE_Q3
-#define GSSS_CS_KNOT_PIPE_Q3 0  // (A/B: 1 = the pipeline in the three-quad builds at three wavefronts per SIMD too, as before round 5)
-#endif
-#ifndef GSSS_CS_KNOT_BARRIER
-#define GSSS_CS_KNOT_BARRIER 2  // knots between scheduling barriers in the knot-dot loop
-#endif
+constexpr int kCsWavesK17 = 3, kCsWavesQ2 = 3, kCsWavesQ3 = 3;
+// lanes per chain below which the screen evaluates two segments per packed instruction (Curve32<.., PACKED>): every group size
+// (sixteen lanes: packed with preloaded constants lost 1 %, packed without them and with the copy of the loop for full curves
+// gains 1.4 %: d = 200 96.24 -> 94.9 ms)
+constexpr int kCsPackedBelow = 64;
+// component quads per lane from which the try evaluation reads all segment constants in one go -- in the sixteen-lane builds
+// only: the four- and eight-lane ones evaluate segments in pairs and take the copy of the loop for full curves instead, which
+// preloading would make spill (round 4: d = 24 27.79 -> 26.58 ms, d = 50 33.90 -> 32.62)
+constexpr int kCsPreloadQ = 2;
+constexpr int kCsKnotBarrier = 2;  // knots between scheduling barriers in the knot-dot loop
 
 template <int L, int NK>
 __host__ __device__ constexpr int curvespec_scratch_doubles()
@@ -91,14 +65,14 @@ __host__ __device__ constexpr int curvespec_scratch_doubles()
     return 2 + 4 * L + 2 * NK;  // U_threshold, U_theta0 | a ring of 8 L try words (4 L doubles of a replayed stream) | the step's double-precision coefficients
 }
 // The tangent u rests in LDS while the tries run where the registers would not hold it beside the try loop's: the 17-knot
-// builds with more than four components per lane.  (Round 3: the 10-knot builds kept parking it at two wavefronts per SIMD, where
+// builds with more than four components per lane, and the three-quad 10-knot builds (three wavefronts per SIMD, kCsWavesQ3).  (Round 3: the 10-knot builds kept parking it at two wavefronts per SIMD, where
 // 256 registers are to be had -- without, <4, 4, 10> takes 254 and <16, 4, 10> 246, nothing spilled: d = 50 35.3 -> 34.9 ms,
 // d = 200 99.4 -> 97.4 ms per 10^8 chain-steps.)
 // (HEAVY: the replay and statistics builds carry more state and keep parking it.)
 template <int Q, int NK, bool HEAVY>
 __host__ __device__ constexpr bool curvespec_parks_u()
 {
-    return Q >= 2 && (NK > 10 || HEAVY || Q >= GSSS_CS_PARK_FROM_Q || (Q == 3 && GSSS_CS_WAVES_Q3 >= 3));
+    return Q >= 2 && (NK > 10 || HEAVY || Q == 3);
 }
 // (R) the tail slot of the tangent rests in LDS beside the quads' -- but for sixteen-lane groups: with its 2 KB the <16, 3, 10, +1>
 // workgroup needs 55.8 KB of LDS, TWO workgroups per CU under a kernel built for three wavefronts per SIMD (the first measurement of
@@ -111,9 +85,9 @@ __host__ __device__ constexpr bool curvespec_parks_tail()
 template <int L, int Q, int NK, bool STATS>
 __host__ __device__ constexpr int curvespec_waves()
 {
-    if (STATS) return GSSS_CS_WAVES_BIG;
-    if (NK > 10) return Q <= 2 ? GSSS_CS_WAVES_K17 : GSSS_CS_WAVES_BIG;
-    return Q == 1 ? GSSS_CS_WAVES : (Q == 2 ? GSSS_CS_WAVES_Q2 : (Q == 3 ? GSSS_CS_WAVES_Q3 : GSSS_CS_WAVES_BIG));
+    if (STATS) return kCsWavesBig;
+    if (NK > 10) return Q <= 2 ? kCsWavesK17 : kCsWavesBig;
+    return Q == 1 ? kCsWaves : (Q == 2 ? kCsWavesQ2 : (Q == 3 ? kCsWavesQ3 : kCsWavesBig));
 }
 template <int L, int Q, int NK, bool HEAVY, int R = 0>
 __host__ __device__ constexpr size_t curvespec_lds_doubles()
@@ -243,7 +217,7 @@ __global__ void __launch_bounds__(kBlock, (curvespec_waves<L, Q, NK, STATS>())) 
         sg[4 * i + 3] = 0.0;
     }
     __syncthreads();
-    Curve32<NK, (L < GSSS_CS_PACKED_BELOW)> c32;
+    Curve32<NK, (L < kCsPackedBelow)> c32;
     c32.stage(reinterpret_cast<float4 *>(sg + 4 * (NK - 1)), sg, k - 1, tb.kappa);
     double *scr = sg + 6 * (size_t)(NK - 1) + (size_t)kScratch * (threadIdx.x / L);
     double *ring = scr + 2;
@@ -342,7 +316,7 @@ __global__ void __launch_bounds__(kBlock, (curvespec_waves<L, Q, NK, STATS>())) 
         const double *knots = lds + opaque;
         Scalar scl = sc;
         scl.seg = knots + (size_t)NK * DPAD;
-        Curve32<NK, (L < GSSS_CS_PACKED_BELOW)> c32s = c32;
+        Curve32<NK, (L < kCsPackedBelow)> c32s = c32;
         c32s.seg32 = reinterpret_cast<const float4 *>(knots + (size_t)NK * DPAD + 4 * (NK - 1));
         // ---------------- draws of the step
         double u[N], u_thr, u_th0;
@@ -446,7 +420,7 @@ __global__ void __launch_bounds__(kBlock, (curvespec_waves<L, Q, NK, STATS>())) 
         for (int r = 0; r < R; ++r) ut[r] = fma(-cz * rnx, xt[r], ut[r]);
         // ---------------- a_r . u = (a_r . w) / |w|, a_r . x; single-precision pack; the doubles parked for decide()
         const bool refresh = !kRecur || s == 0 || ((step0 + (uint64_t)s) % kCoefRefresh) == 0;
-        float q[Curve32<NK, (L < GSSS_CS_PACKED_BELOW)>::kFloats];
+        float q[Curve32<NK, (L < kCsPackedBelow)>::kFloats];
         {
             double pw = 0.0;
 #pragma unroll
@@ -463,7 +437,7 @@ __global__ void __launch_bounds__(kBlock, (curvespec_waves<L, Q, NK, STATS>())) 
             // from 5.9 to 3.7 MB per XCD, under the 4 MB of its L2 (34.2 -> 8.3 GB of HBM traffic per launch, 80.3 -> 74.1 ms); d = 50
             // 4.19 -> 2.25 GB, 26.0 -> 25.4 ms; d = 40 / 100 / 160 +0.5 .. 1.3 %, d = 80 -0.8 % (profiles/r05_ab_knot_pipe_q3.log).
             // Two quads (three wavefronts, d = 24: -1 % without) and four quads (two wavefronts) keep it.
-            constexpr bool kPipe = GSSS_CS_KNOT_PIPE && Q >= 2 && !(Q == 3 && curvespec_waves<L, Q, NK, STATS>() >= 3 && !REPLAY && !GSSS_CS_KNOT_PIPE_Q3);
+            constexpr bool kPipe = Q >= 2 && !(Q == 3 && curvespec_waves<L, Q, NK, STATS>() >= 3 && !REPLAY);
             if constexpr (kPipe) {
                 // (sixteen lanes x sixteen components: half a row ahead -- a whole one spills 12 bytes a lane at two wavefronts per SIMD)
                 constexpr int kAhead = (L >= 16 && Q >= 4) ? N / 4 : N / 2;
@@ -563,7 +537,7 @@ __global__ void __launch_bounds__(kBlock, (curvespec_waves<L, Q, NK, STATS>())) 
                     else
                         coef[2 * r + 1] = au;
                     // two knots at a time: left alone the scheduler runs all NK reduction chains side by side (4 NK registers)
-                    if (GSSS_CS_KNOT_BARRIER > 0 && r % GSSS_CS_KNOT_BARRIER == GSSS_CS_KNOT_BARRIER - 1) __builtin_amdgcn_sched_barrier(0);  // (five knots at a time: measured, no change)
+                    if (r % kCsKnotBarrier == kCsKnotBarrier - 1) __builtin_amdgcn_sched_barrier(0);  // (five knots at a time: measured, no change)
                 }
             }
 #pragma unroll
@@ -665,7 +639,7 @@ __global__ void __launch_bounds__(kBlock, (curvespec_waves<L, Q, NK, STATS>())) 
             const bool mine = !done && g < valid && t_base + g < max_tries;
             // (Q >= 2: two wavefronts per SIMD and registers to spare -- the segments' constants are read from LDS in one go, one
             // round trip per evaluation instead of one per segment: 38.3 -> 37.0 ms at d = 50, 105.4 -> 103.8 at d = 200)
-            const float my_b = c32s.template best32<(Q >= GSSS_CS_PRELOAD_Q && L >= GSSS_CS_PACKED_BELOW)>(q, c32f, s32);
+            const float my_b = c32s.template best32<(Q >= kCsPreloadQ && L >= kCsPackedBelow)>(q, c32f, s32);
             const float gap = my_b - q[2 * NK];
             int verdict = mine ? (gap < -q[2 * NK + 1] ? -1 : (gap > q[2 * NK + 1] ? 1 : 0)) : -1;
             // first try of the group that is not certainly rejected; an undecided one is decided in double precision by its lane
@@ -798,29 +772,14 @@ int do_curvespec(const TargetBlock &tb, const RunBlock &rb, bool replay, hipStre
             return GSSS_E_UNSUPPORTED;
         }
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
-    const int64_t per_block = kBlock / L;
-    const int64_t n_chunks = (rb.n_chains + per_block - 1) / per_block;
+    if (int rc = allow_lds("curvespec", kern, lds)) return rc;
+    const int64_t n_chunks = ceil_div(rb.n_chains, kBlock / L);
     // more chunks than the chip holds at once: a grid of the resident workgroups takes (chunk, step slice) tickets (SliceSched)
     const SlicePlan plan = plan_slices(kern, lds, rb, n_chunks, !replay, st);
     RunBlock rbl = rb;
     rbl.sched = plan.ws;
     rbl.slice_steps = plan.slice_steps;
-    hipLaunchKernelGGL(kern, dim3((unsigned)plan.grid), dim3(kBlock), lds, st, tb, rbl);
-    hipError_t e = hipGetLastError();
-    if (plan.ws) (void)hipFreeAsync(plan.ws, st);
-    if (e != hipSuccess) {
-        set_error("curvespec kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    return launch_kernel("curvespec", kern, plan.grid, lds, st, plan.ws, tb, rbl);
 }
 
 }  // namespace gsss

@@ -170,6 +170,38 @@ struct SliceSched {
 
 constexpr size_t slice_sched_bytes(int64_t n_chunks, int64_t n_chains) { return 4 * (size_t)(2 + n_chunks + n_chains); }
 
+// ------------------------------------------------------------------------------------------
+// Host side: one kernel launch.  Every launcher raises the kernel's dynamic-LDS limit (allow_lds) before it asks the runtime
+// anything about the kernel (the occupancy queries of the slice planners), then launches through launch_kernel.
+// (gsss_last_launch is recorded by plan_slices, plan_partial_round and do_screened_numpy only, never here.)
+// ------------------------------------------------------------------------------------------
+void set_error(const char *fmt, ...);  // gsss_capi.hip
+constexpr size_t kDefaultLdsBytes = 48 * 1024;  // dynamic LDS a kernel may be launched with without raising its attribute
+constexpr size_t kMaxLdsBytes = 160 * 1024;     // a workgroup's LDS on gfx950
+constexpr int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+template <class Kern>
+int allow_lds(const char *family, Kern kern, size_t lds)
+{
+    if (lds <= kDefaultLdsBytes) return GSSS_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) return GSSS_OK;
+    set_error("%s kernel: raising its dynamic LDS to %zu B failed: %s", family, lds, hipGetErrorString(e));
+    return GSSS_E_HIP;
+}
+
+// `grid` workgroups of kBlock threads; `ws`: the launch's slice-ticket workspace (SlicePlan::ws) or NULL, freed in stream order
+template <class Kern, class... Args>
+int launch_kernel(const char *family, Kern kern, int64_t grid, size_t lds, hipStream_t st, void *ws, const Args &...args)
+{
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, args...);
+    const hipError_t e = hipGetLastError();
+    if (ws) (void)hipFreeAsync(ws, st);
+    if (e == hipSuccess) return GSSS_OK;
+    set_error("%s kernel launch failed: %s", family, hipGetErrorString(e));
+    return GSSS_E_HIP;
+}
+
 // Host side: should this launch be sliced, and on how many workgroups?  Sliced when the chunks do not fit the chip at once (a
 // last, partial round would otherwise run on a nearly empty chip: measured 15 % of the curve kernels' time at 10^5 chains) and
 // there are at least two slices.  The workspace is allocated, zeroed and freed in stream order; a failed allocation falls back

@@ -721,8 +721,6 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
 }
 
 // host side: launch one instantiation
-void set_error(const char *fmt, ...);
-
 template <int D, class TP, bool REPLAY>
 int do_fast_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 {
@@ -731,23 +729,9 @@ int do_fast_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     if constexpr (!REPLAY) {  // running statistics: a build of its own (the plain kernel carries none of it)
         if (rb.stats != nullptr) kern = fast_kernel<D, TP, false, true>;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
+    if (int rc = allow_lds("fast", kern, lds)) return rc;
     const int per_block = rb.spread ? kBlock / 64 : fast_chains_per_block<D, TP>();
-    const int64_t grid = (rb.n_chains + per_block - 1) / per_block;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("fast kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    return launch_kernel("fast", kern, ceil_div(rb.n_chains, per_block), lds, st, nullptr, tb, rb);
 }
 
 // numpy's stream, one lane per chain (fast_kernel<..., NUMPY>)
@@ -756,22 +740,8 @@ int do_fast_numpy(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 {
     const size_t lds = (TP::lds_doubles() + kTabLds + NumpyDraws<LaneVec<D>>::kLdsDoubles) * sizeof(double);
     auto kern = rb.stats != nullptr ? fast_kernel<D, TP, true, true, true> : fast_kernel<D, TP, true, false, true>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
-    const int per_block = rb.spread ? kBlock / 64 : kBlock;
-    const int64_t grid = (rb.n_chains + per_block - 1) / per_block;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("fast kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    if (int rc = allow_lds("fast", kern, lds)) return rc;
+    return launch_kernel("fast", kern, ceil_div(rb.n_chains, rb.spread ? kBlock / 64 : kBlock), lds, st, nullptr, tb, rb);
 }
 
 template <int D, class TP>
@@ -1307,7 +1277,7 @@ int do_coopfast(const TargetBlock &tb, const RunBlock &rb, bool replay, hipStrea
         return GSSS_E_UNSUPPORTED;
     }
     const size_t lds = (coop_param_doubles<TP>(tb.d) + (size_t)TP::kScratchPerGroup * (kBlock / V::L)) * sizeof(double);
-    if (lds > 160 * 1024) {
+    if (lds > kMaxLdsBytes) {
         set_error("target parameters need %zu B of LDS", lds);
         return GSSS_E_UNSUPPORTED;
     }
@@ -1319,29 +1289,14 @@ int do_coopfast(const TargetBlock &tb, const RunBlock &rb, bool replay, hipStrea
         }
         kern = coopfast_kernel<V, TP, false, true>;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
-    const int64_t per_block = kBlock / V::L;
-    const int64_t n_chunks = (rb.n_chains + per_block - 1) / per_block;
+    if (int rc = allow_lds("cooperative fast", kern, lds)) return rc;
+    const int64_t n_chunks = ceil_div(rb.n_chains, kBlock / V::L);
     // more chunks than the chip holds at once: one workgroup per (chunk, step slice), tickets (SliceSched, gsss_device.h)
     const SlicePlan plan = plan_slices(kern, lds, rb, n_chunks, !replay, st);
     RunBlock rbl = rb;
     rbl.sched = plan.ws;
     rbl.slice_steps = plan.slice_steps;
-    hipLaunchKernelGGL(kern, dim3((unsigned)plan.grid), dim3(kBlock), lds, st, tb, rbl);
-    hipError_t e = hipGetLastError();
-    if (plan.ws) (void)hipFreeAsync(plan.ws, st);
-    if (e != hipSuccess) {
-        set_error("cooperative fast kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    return launch_kernel("cooperative fast", kern, plan.grid, lds, st, plan.ws, tb, rbl);
 }
 
 }  // namespace gsss
@@ -1600,22 +1555,8 @@ int do_wave(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     const size_t lds = (TP::lds_doubles() + kTabLds + (numpy ? NumpyDraws<LaneVec<D>>::kLdsDoubles : 0)) * sizeof(double);
     auto kern = numpy ? wave_kernel<D, TP, true, false> : wave_kernel<D, TP, false, false>;
     if (rb.stats != nullptr) kern = numpy ? wave_kernel<D, TP, true, true> : wave_kernel<D, TP, false, true>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
-    const int64_t grid = (rb.n_chains + kBlock / 64 - 1) / (kBlock / 64);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("wave kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    if (int rc = allow_lds("wave", kern, lds)) return rc;
+    return launch_kernel("wave", kern, ceil_div(rb.n_chains, kBlock / 64), lds, st, nullptr, tb, rb);
 }
 
 }  // namespace gsss

@@ -38,8 +38,6 @@ using VC64x32 = CoopVec<64, 32>;
     X(14, VC64x16, "coop64x16") \
     X(15, VC64x32, "coop64x32")
 
-constexpr size_t kMaxLdsBytes = 160 * 1024;
-
 struct VecInfo {
     int id, L, N, dpad;
     bool exact_dim;
@@ -56,8 +54,6 @@ template <template <class> class TT>
 int launch_run(int vec_id, int draws, const TargetBlock &tb, const RunBlock &rb, hipStream_t st);
 template <template <class> class TT>
 int launch_logprob(int vec_id, const TargetBlock &tb, const double *x, int64_t n, double *out, bool grad, hipStream_t st);
-
-void set_error(const char *fmt, ...);
 
 #define GSSS_HIP_TRY(expr)                                                              \
     do {                                                                                \
@@ -79,14 +75,9 @@ int do_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     }
     auto kern = run_kernel<V, TT, DR, false>;
     if (rb.stats != nullptr) kern = run_kernel<V, TT, DR, true>;  // running statistics: a second build, so that the plain kernels carry none of it
-    if (lds > 48 * 1024)
-        GSSS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = allow_lds("run", kern, lds)) return rc;
     const int64_t per_block = (V::L == 1 && rb.spread) ? kBlock / 64 : kBlock / V::L;
-    const int64_t grid = (rb.n_chains + per_block - 1) / per_block;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rb);
-    GSSS_HIP_TRY(hipGetLastError());
-    return GSSS_OK;
+    return launch_kernel("run", kern, ceil_div(rb.n_chains, per_block), lds, st, nullptr, tb, rb);
 }
 
 template <class V, template <class> class TT>
@@ -99,14 +90,8 @@ int do_logprob(const TargetBlock &tb, const double *x, int64_t n, double *out, b
         return GSSS_E_UNSUPPORTED;
     }
     auto kern = grad ? logprob_kernel<V, TT, true> : logprob_kernel<V, TT, false>;
-    if (lds > 48 * 1024)
-        GSSS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t per_block = kBlock / V::L;
-    const int64_t grid = (n + per_block - 1) / per_block;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, x, n, out);
-    GSSS_HIP_TRY(hipGetLastError());
-    return GSSS_OK;
+    if (int rc = allow_lds("logprob", kern, lds)) return rc;
+    return launch_kernel("logprob", kern, ceil_div(n, kBlock / V::L), lds, st, nullptr, tb, x, n, out);
 }
 
 // Each target's translation unit expands this once.

@@ -191,28 +191,13 @@ int do_mh(const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStrea
 {
     using T = TT<V>;
     const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>() + DR<V>::kLdsDoubles) * sizeof(double);
-    if (lds > 160 * 1024) {
+    if (lds > kMaxLdsBytes) {
         set_error("target parameters need %zu B of LDS", lds);
         return GSSS_E_UNSUPPORTED;
     }
     auto kern = mh_kernel<V, TT, DR, SAMPLER>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
-    const int64_t per_block = kBlock / V::L;
-    const int64_t grid = (rb.n_chains + per_block - 1) / per_block;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rb, mb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("MH kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    if (int rc = allow_lds("MH", kern, lds)) return rc;
+    return launch_kernel("MH", kern, ceil_div(rb.n_chains, kBlock / V::L), lds, st, nullptr, tb, rb, mb);
 }
 
 template <template <class> class TT>

@@ -28,16 +28,6 @@
 #include "gsss_fast.h"
 #include "gsss_screen_consts.h"
 
-#ifndef GSSS_VMF_ONE_BUILD
-#define GSSS_VMF_ONE_BUILD 1  // (0: without the one-chain-per-lane build of the K = 7 .. 10 mixtures, A/B)
-#endif
-#ifndef GSSS_VMF_ONE_ALL
-#define GSSS_VMF_ONE_ALL 0  // (measurement: build it for every bucket; GSSS_ONE_PER_LANE=2 then runs it)
-#endif
-#ifndef GSSS_SCREEN_REGEN_THR
-#define GSSS_SCREEN_REGEN_THR 1  // (A/B: 0 parks the threshold uniform of the S^2 mixtures as round 2 did)
-#endif
-
 namespace gsss {
 
 // A try that stopped: accepted for sure / double precision decides.  Its theta rests in the end of the bracket it would
@@ -90,27 +80,27 @@ struct ScreenVmf : FastVmf<D, KC> {
     // 18 instead of 28 words of parked state at K = 10, three workgroups per CU instead of two (and the register budget
     // of three wavefronts per SIMD asked of the compiler: 170 -> 168)
     static constexpr int kParkSkip = KC >= 6 ? 2 * KC : 0;  // (K = 3: 36.5 against 34.8 ms with it -- four workgroups per CU fit anyway)
-    static constexpr int kMinWaves = D > 10 ? ((D <= 12 && KC <= 3) ? 3 : 2) : (KC >= 6 ? 3 : ((GSSS_SCREEN_REGEN_THR && D == 3 && KC <= 3) ? 5 : 1));
+    static constexpr int kMinWaves = D > 10 ? ((D <= 12 && KC <= 3) ? 3 : 2) : (KC >= 6 ? 3 : ((D == 3 && KC <= 3) ? 5 : 1));
     // K >= 6 forms the 2 K coefficients again at take-up (kParkSkip), which makes a swap as dear as a pair of tries: swapping only
     // when 24 lanes want to is worth 9 % (K = 10, kappa = 500: 56.6 -> 51.7 ms per 10^9 chain-steps; 12: 52.5, 32: 59.2, 44: 71.7);
     // with the cheap swaps of K <= 5 and of the Bingham target waiting costs more than it saves (27.7 -> 28.3 / 28.6 ms at 12 / 24).
     static constexpr int kTradeMin = KC >= 6 ? 24 : 1;
     static constexpr bool kCompact = false;
     // The one-chain-per-lane BUILD (screened_kernel<.., STAGE>: no code for a parked chain; do_screened_run) at any ensemble size
-    // where it was measured ahead at 10^6 chains (tools/bench_vmf_pure_one.py, profiles/r04_vmf_pure_one.log): bucket 10 at every
+    // where it was measured ahead at 10^6 chains (profiles/r04_vmf_pure_one.log): bucket 10 at every
     // d (+6 .. 11 %; cfg5, S^2 K = 10 kappa = 500: 48.9 -> 46.8 ms), bucket 6 up to d = 8 (+4 .. 10 %), bucket 16 up to d = 5 (+7 %),
     // bucket 4 on S^2 (+7 %), bucket 3 at d = 4 (+4.5 %).  The README kernel (S^2, K = 3) stays with two chains per lane (24.1
     // against 24.7 ms); everything else is within 1 % either way and keeps the old rule.
     static constexpr bool kOneAhead = KC == 10 || (KC == 6 && D <= 8) || (KC == 16 && D <= 5) || (KC == 4 && D == 3) || (KC == 3 && D == 4);
-    static constexpr bool kStageRows = GSSS_VMF_ONE_BUILD && (kOneAhead || GSSS_VMF_ONE_ALL);
+    static constexpr bool kStageRows = kOneAhead;
     static constexpr bool kHoldRows = false;  // ... without the rows held back in LDS (registers)
-    static constexpr bool kPreferOne = GSSS_VMF_ONE_BUILD && kOneAhead;
+    static constexpr bool kPreferOne = kOneAhead;
     static constexpr int kNumpyWaves = (KC >= 10 || (D >= 9 && KC >= 6)) ? 2 : ((D <= 4 && KC <= 3) ? 4 : 3);  // wavefronts per SIMD of the numpy-stream build: without scratch, but for the smallest
                                                    // shapes, where a fourth wavefront is worth 12-20 spilled bytes (README target 40.9 -> 38.7 ms)
     // S^2, K <= 3 (the README target, BASELINE cfg2): the threshold uniform is not parked -- an undecided try draws it again
     // from the counter-based stream -- which makes the parked state 15 words: five workgroups per CU instead of four (the
     // kernel needs 95 registers: five wavefronts per SIMD fit)
-    static constexpr bool kRegenThr = GSSS_SCREEN_REGEN_THR && D == 3 && KC <= 3;
+    static constexpr bool kRegenThr = D == 3 && KC <= 3;
     __device__ __forceinline__ void retail(float (&)[kCoef32Floats]) const {}
     __device__ __forceinline__ void refill(const double (&x)[D], const double (&u)[D], float (&q)[kCoef32Floats]) const
     {
@@ -1153,10 +1143,7 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     // A slice's state, counters and flags go to the chunk's next slice: written through (SliceSched::hand_over), so that
     // publishing them needs no write-back of the whole L2 (the statistics build hands its accumulators over with plain stores
     // and keeps the release).
-#ifndef GSSS_HAND_OVER_PLAIN  // (A/B builds: 1 = plain stores and a release, as the group kernels do)
-#define GSSS_HAND_OVER_PLAIN 0
-#endif
-    constexpr bool kThrough = !STATS && !GSSS_HAND_OVER_PLAIN;
+    constexpr bool kThrough = !STATS;
     auto put_out = [&](auto *p, auto v) {
         if (kThrough && sliced)
             SliceSched::hand_over(p, v);
@@ -1237,16 +1224,9 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         const int n_live = __popcll(live);
         // the service phase (double precision) costs several try iterations (single precision): it runs when three
         // quarters of the live lanes wait for it (or seven eighths have something for it)
-#ifndef GSSS_SVC_WAIT_NUM
-#define GSSS_SVC_WAIT_NUM 3
-#define GSSS_SVC_WAIT_DEN 4
-#endif
-#ifndef GSSS_SVC_PEND_NUM
-#define GSSS_SVC_PEND_NUM 7
-#define GSSS_SVC_PEND_DEN 8
-#endif
-        const bool service = pend != 0ull && (GSSS_SVC_WAIT_DEN * __popcll(waiting) >= GSSS_SVC_WAIT_NUM * n_live ||
-                                              GSSS_SVC_PEND_DEN * __popcll(pend) >= GSSS_SVC_PEND_NUM * n_live);
+        constexpr int kSvcWaitNum = 3, kSvcWaitDen = 4, kSvcPendNum = 7, kSvcPendDen = 8;
+        const bool service = pend != 0ull && (kSvcWaitDen * __popcll(waiting) >= kSvcWaitNum * n_live ||
+                                              kSvcPendDen * __popcll(pend) >= kSvcPendNum * n_live);
         if (service) {
             if (kPark && !needs_service(cur.status) && needs_service(parked_status)) trade();  // bring the waiting chain in
             if (is_final(cur.status)) finalise();
@@ -1276,26 +1256,14 @@ int do_screened_numpy(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 {
     const size_t lds = (TP::lds_doubles() + kTabLds + NumpyDraws<LaneVec<D>>::kLdsDoubles) * sizeof(double);
     auto kern = rb.stats != nullptr ? screened_kernel<D, TP, true, true, false, true> : screened_kernel<D, TP, true, false, false, true>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
+    if (int rc = allow_lds("screened", kern, lds)) return rc;
     RunBlock rbl = rb;
     rbl.one_per_lane = 1;
     rbl.stage_rows = 0;
     rbl.sched = nullptr;
-    const int64_t grid = (rb.n_chains + kBlock - 1) / kBlock;
+    const int64_t grid = ceil_div(rb.n_chains, kBlock);
     last_launch() = LaunchInfo{grid, 0, 0.0};
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rbl);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("screened kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    return launch_kernel("screened", kern, grid, lds, st, nullptr, tb, rbl);
 }
 
 template <int D, class TP, bool REPLAY>
@@ -1306,14 +1274,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     if constexpr (!REPLAY) {  // running statistics: a build of its own (the plain kernel carries none of it)
         if (rb.stats != nullptr) kern = screened_kernel<D, TP, false, true>;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
+    if (int rc = allow_lds("screened", kern, lds)) return rc;
     int per_block = screen_parks<D, TP>() ? 2 * kBlock : kBlock;
     // Small and mid-size ensembles run ONE chain per lane (256-chain workgroups, the lane's second slot empty): a second
     // wavefront somewhere else is worth more than a lane's second chain, and rounds of workgroups half as long fill the chip
@@ -1332,7 +1293,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
         if (env_one && env_one[0] == '2')
             one_per_lane = true;
         else if ((resident = resident_workgroups(reinterpret_cast<const void *>(kern), lds, &per_cu)) >= 1) {
-            const int64_t b2 = (rb.n_chains + 2 * kBlock - 1) / (2 * kBlock);
+            const int64_t b2 = ceil_div(rb.n_chains, 2 * kBlock);
             one_per_lane = 20 * b2 < 27 * resident;
             // ... and at ANY size where the LDS of the parked chains is what limits the workgroups per CU: without it more
             // wavefronts are resident, and the hardware's switching between them beats the lanes' own between two chains
@@ -1346,7 +1307,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     // The one-chain-per-lane BUILD (below) is ahead of two chains per lane at 10^6 chains too for most shapes that have it
     // (TP::kStageRows): TP::kPreferOne says where.  Bingham targets (tools/bench_pure_one.py, profiles/r04_bingham_pure_one.log):
     // eigenbasis d = 5 .. 7, 9, 10 +3 .. 5 %, dense d = 3 .. 5, 7 +4 %, d = 8 +22 %, d = 10 +8 %; behind at eigenbasis d = 4 (-2 %) and
-    // dense d = 6 (-10 %: 170 registers, two wavefronts).  Mixtures (tools/bench_vmf_pure_one.py, profiles/r04_vmf_pure_one.log):
+    // dense d = 6 (-10 %: 170 registers, two wavefronts).  Mixtures (profiles/r04_vmf_pure_one.log):
     // ScreenVmf::kOneAhead.
     if constexpr (!REPLAY && TP::kStageRows && D <= 10) {
         if (TP::kPreferOne && !(env_one && env_one[0] == '0') && rb.stats == nullptr) one_per_lane = true;
@@ -1361,7 +1322,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
         const char *env_st = getenv("GSSS_STATS_ONCHIP");
         if (rb.stats != nullptr && !(env_st && env_st[0] == '0') && rb.stats_lags <= kStatsMaxLags) {
             const size_t ring = (size_t)rb.stats_lags * kBlock;
-            if ((TP::lds_doubles() + kTabLds + ring) * sizeof(double) <= (size_t)160 * 1024) {  // (a workgroup's LDS on gfx950)
+            if ((TP::lds_doubles() + kTabLds + ring) * sizeof(double) <= kMaxLdsBytes) {
                 stats_onchip = 1;
                 stats_ring = ring;
                 one_per_lane = true;
@@ -1386,7 +1347,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
                     const size_t lds_staged = lds + (size_t)(kStageP - 1) * D * kBlock * sizeof(double);
                     if (resident_workgroups(reinterpret_cast<const void *>(kern_one), lds_staged) >= resident_workgroups(reinterpret_cast<const void *>(kern_one), lds)) {
                         // (the attribute first: rows are held back only if the launch can have the LDS for them)
-                        const bool can = lds_staged <= 48 * 1024 ||
+                        const bool can = lds_staged <= kDefaultLdsBytes ||
                                          hipFuncSetAttribute(reinterpret_cast<const void *>(kern_one), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_staged) == hipSuccess;
                         if (can) {
                             stage_rows = true;
@@ -1399,14 +1360,9 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
             }
         }
     }
-    if (lds > 48 * 1024) {  // the kernel that IS launched, with the LDS it is launched with (the one-chain-per-lane build got none)
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu B of LDS) failed: %s", lds, hipGetErrorString(ea));
-            return GSSS_E_HIP;
-        }
-    }
-    const int64_t n_chunks = (rb.n_chains + per_block - 1) / per_block;
+    // the kernel that IS launched, with the LDS it is launched with (the one-chain-per-lane build got none)
+    if (int rc = allow_lds("screened", kern, lds)) return rc;
+    const int64_t n_chunks = ceil_div(rb.n_chains, per_block);
     // a small last round of workgroups is cut into step slices (plan_partial_round, gsss_device.h)
     plan = plan_partial_round(kern, lds, rb, n_chunks, !REPLAY && screen_parks<D, TP>(), st, first);
     RunBlock rbl = rb;
@@ -1422,14 +1378,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, lds);
         fprintf(stderr, "gsss: screened kernel: %zu B of LDS per workgroup, %d workgroups per CU, grid %lld\n", lds, per_cu, (long long)grid);
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rbl);
-    hipError_t e = hipGetLastError();
-    if (plan.ws) (void)hipFreeAsync(plan.ws, st);
-    if (e != hipSuccess) {
-        set_error("screened kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    return launch_kernel("screened", kern, grid, lds, st, plan.ws, tb, rbl);
 }
 
 }  // namespace gsss

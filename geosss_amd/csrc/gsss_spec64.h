@@ -434,22 +434,8 @@ int do_curve64(const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream
         }
         kern = curve64_kernel<NV, false, true>;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return GSSS_E_HIP;
-        }
-    }
-    const int64_t grid = (rb.n_chains + kBlock / 64 - 1) / (kBlock / 64);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, st, tb, rb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("curve64 kernel launch failed: %s", hipGetErrorString(e));
-        return GSSS_E_HIP;
-    }
-    return GSSS_OK;
+    if (int rc = allow_lds("curve64", kern, lds)) return rc;  // (no LDS pre-check: beyond a workgroup's LDS this fails, GSSS_E_HIP)
+    return launch_kernel("curve64", kern, ceil_div(rb.n_chains, kBlock / 64), lds, st, nullptr, tb, rb);
 }
 
 }  // namespace gsss

@@ -11,14 +11,12 @@
 #include <string.h>
 
 #include "../../include/gsss.h"
+#include "gsss_device.h"
 #include "gsss_screen_consts.h"
 
 namespace gsss {
-void set_error(const char *fmt, ...);  // gsss_capi.hip
-
 namespace {
 
-constexpr int kSweepBlock = 256;
 constexpr int kSweepOut = 4;
 
 __device__ void atomic_max_double(double *p, double v)
@@ -42,7 +40,7 @@ __device__ __forceinline__ double half_ulp(float x)
 }
 
 // which: 0 sin / cos of x revolutions, 1 2^x, 2 log2 x, 3 sqrt x.  Bit patterns lo .. lo + count - 1 of one sign.
-__global__ void __launch_bounds__(kSweepBlock) f32_sweep_kernel(uint32_t lo_bits, uint64_t count, int which, double *acc)
+__global__ void __launch_bounds__(kBlock) f32_sweep_kernel(uint32_t lo_bits, uint64_t count, int which, double *acc)
 {
     double e[kSweepOut] = {0.0, 0.0, 0.0, 0.0};
     const double two_pi = 6.283185307179586476925286766559, inv_ln2 = 1.4426950408889634;
@@ -141,8 +139,7 @@ int gsss_f32_error_sweep(int32_t which, double *out_host, uint64_t *n_swept_out,
             memcpy(&ua, &ranges[which][r].a, 4);
             memcpy(&ub, &ranges[which][r].b, 4);
             const uint64_t count = (uint64_t)(ub - ua) + 1;
-            hipLaunchKernelGGL(f32_sweep_kernel, dim3(16384), dim3(kSweepBlock), 0, st, ua, count, (int)which, acc);
-            if (hipGetLastError() != hipSuccess) rc = GSSS_E_HIP;
+            rc = launch_kernel("f32 sweep", f32_sweep_kernel, 16384, 0, st, nullptr, ua, count, (int)which, acc);
             swept += count;
         }
         if (rc == GSSS_OK && (hipMemcpyAsync(out_host, acc, sizeof(zero), hipMemcpyDeviceToHost, st) != hipSuccess ||

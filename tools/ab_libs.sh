@@ -1,6 +1,6 @@
 #!/bin/bash
-# Run ON THE GPU BOX: A/B timing of side-by-side builds (python -m geosss_amd.build --out geosss_amd/libgsss_<tag>.so with
-# GSSS_HIPCC_FLAGS=-D...): kernel_ms of the given workloads under each library.  Usage: tools/ab_libs.sh "<libs>" "<workload:chains> ..."
+# Run ON THE GPU BOX: A/B timing of side-by-side builds (tools/build_variant.sh, or python -m geosss_amd.build --out
+# geosss_amd/libgsss_<tag>.so): kernel_ms of the given workloads under each library.  Usage: tools/ab_libs.sh "<libs>" "<workload:chains> ..."
 for lib in $1; do
   for wc in $2; do
     wl=${wc%%:*}; n=${wc##*:}

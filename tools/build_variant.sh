@@ -1,6 +1,7 @@
 #!/bin/bash
-# A side-by-side library that differs from the built one in ONE translation unit compiled with extra flags (A/B of kernel
-# variants behind -D macros): the other objects are copied, so a variant costs one compile and a link.
+# A side-by-side library that differs from the built one in ONE translation unit, compiled from the tree as it is now with
+# extra hipcc flags (A/B of an edited source or of a code-generation option): the other objects are copied, so a variant costs
+# one compile and a link.
 # Usage: tools/build_variant.sh <tag> <source.hip> <flags...>   ->  geosss_amd/libgsss_<tag>.so  (load with GSSS_HIP_LIB)
 set -eu
 TAG=$1; SRC=$2; shift 2
