@@ -130,6 +130,18 @@ static int select_vec_for(const gsss::TargetBlock &tb, int variant)
         if (v[i].id == vec) dpad = (size_t)v[i].dpad;
     if (dpad >= 256) return vec;
     size_t rows = 0;
+    if (tb.kind == GSSS_MIXTURE) {  // the whole launch: component slots, Bingham scratch rows, draw tables and rows (Mixture)
+        int L = 1;
+        for (int i = 0; i < n; ++i)
+            if (v[i].id == vec) L = v[i].L;
+        const MixInfo mi = mix_info(tb);
+        const size_t need = (size_t)mi.n * 8 + (L > 1 ? (dpad + 1) * (size_t)(kBlock / L) : 0) + kMixDrawsReserve +
+                            (size_t)mi.rows * dpad + (size_t)mi.extra;
+        if (need * sizeof(double) <= kMaxLdsBytes) return vec;
+        for (int i = 0; i < n; ++i)
+            if (!v[i].exact_dim && v[i].dpad >= 256 && tb.d <= v[i].dpad) return v[i].id;
+        return vec;
+    }
     switch (tb.kind) {
     case GSSS_VMF_MIXTURE: rows = (size_t)tb.k * dpad + (size_t)tb.k; break;
     case GSSS_BINGHAM: rows = (size_t)(tb.d + 1) * dpad; break;
@@ -367,6 +379,7 @@ static int fast_dispatch(const gsss::TargetBlock &tb, const gsss::RunBlock &rb, 
     case GSSS_VMF_MIXTURE: return gsss::launch_fast_vmf(tb, rb, replay, probe, st);
     case GSSS_BINGHAM: return gsss::launch_fast_bingham(tb, rb, replay, probe, st);
     case GSSS_CURVE_VMF: return gsss::launch_fast_curve(tb, rb, replay, probe, st);
+    case GSSS_MIXTURE: return gsss::launch_fast_mixture(tb, rb, replay, probe, st);
     }
     if (!probe) gsss::set_error("fast mode is not built for target kind %d", tb.kind);
     return GSSS_E_UNSUPPORTED;
@@ -385,39 +398,12 @@ struct gsss_target {
     int cpd_variant;  // GSSS_CPD: which registration kernel (neighbour-list size, uniform source weights)
 };
 
-extern "C" {
-
-int gsss_abi_version(void) { return GSSS_ABI_VERSION; }
-
-const char *gsss_last_error(void) { return g_err; }
-
-int gsss_device_count(void)
+// The parameter blob of one target (layout per kind: TargetBlock::blob); gsss_target_create, and per component
+// gsss_target_create_mixture
+static int pack_target(const gsss_target_desc *desc, std::vector<double> &blob, bool &bingham_diagonal, double &scale,
+                       int &cpd_variant)
 {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return n;
-}
-
-int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **out)
-{
-    if (!desc || !out) {
-        set_error("null argument");
-        return GSSS_E_INVALID;
-    }
-    *out = nullptr;
     const int d = desc->d, k = desc->k;
-    if (d < 2) {
-        set_error("d must be >= 2 (got %d)", d);
-        return GSSS_E_INVALID;
-    }
-    if (select_vec(d, 0) < 0) return GSSS_E_UNSUPPORTED;  // before any parameter array is touched
-    std::vector<double> blob;
-    bool bingham_diagonal = false;
-    double scale = 0.0;
-    int cpd_variant = 0;
     switch (desc->kind) {
     case GSSS_VMF_MIXTURE:
         if (k < 1 || !desc->mu || !desc->logc) {
@@ -513,6 +499,43 @@ int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **o
         set_error("unknown target kind %d", desc->kind);
         return GSSS_E_INVALID;
     }
+    return GSSS_OK;
+}
+
+extern "C" {
+
+int gsss_abi_version(void) { return GSSS_ABI_VERSION; }
+
+const char *gsss_last_error(void) { return g_err; }
+
+int gsss_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return n;
+}
+
+int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **out)
+{
+    if (!desc || !out) {
+        set_error("null argument");
+        return GSSS_E_INVALID;
+    }
+    *out = nullptr;
+    const int d = desc->d, k = desc->k;
+    if (d < 2) {
+        set_error("d must be >= 2 (got %d)", d);
+        return GSSS_E_INVALID;
+    }
+    if (select_vec(d, 0) < 0) return GSSS_E_UNSUPPORTED;  // before any parameter array is touched
+    std::vector<double> blob;
+    bool bingham_diagonal = false;
+    double scale = 0.0;
+    int cpd_variant = 0;
+    if (int rc = pack_target(desc, blob, bingham_diagonal, scale, cpd_variant)) return rc;
     int ndev = gsss_device_count();
     if (ndev <= 0 || device < 0 || device >= ndev) {
         set_error("device %d not available (%d HIP devices visible)", device, ndev);
@@ -549,6 +572,134 @@ int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **o
     return GSSS_OK;
 }
 
+int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_components, const double *log_weights, int device,
+                               gsss_target **out)
+{
+    if (!components || !log_weights || !out) {
+        set_error("null argument");
+        return GSSS_E_INVALID;
+    }
+    *out = nullptr;
+    if (n_components < 1) {
+        set_error("a mixture needs at least one component (got %d)", n_components);
+        return GSSS_E_INVALID;
+    }
+    if (n_components > kMixMaxComponents) {
+        set_error("a mixture takes at most %d components (got %d)", kMixMaxComponents, n_components);
+        return GSSS_E_UNSUPPORTED;
+    }
+    const int d = components[0].d;
+    if (d < 2) {
+        set_error("d must be >= 2 (got %d)", d);
+        return GSSS_E_INVALID;
+    }
+    for (int c = 0; c < n_components; ++c) {
+        const int kind = components[c].kind;
+        if (kind == GSSS_CPD) {
+            set_error("component %d: registration targets are not built as mixture components", c);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (kind != GSSS_VMF_MIXTURE && kind != GSSS_BINGHAM && kind != GSSS_CURVE_VMF) {
+            set_error("component %d: kind %d is not a mixture component (vMF mixture, Bingham or curve-vMF; nested mixtures are "
+                      "flattened by the caller)", c, kind);
+            return GSSS_E_INVALID;
+        }
+        if (components[c].d != d) {
+            set_error("mixture components must share d (component 0 has d=%d, component %d d=%d)", d, c, components[c].d);
+            return GSSS_E_INVALID;
+        }
+        if (log_weights[c] != log_weights[c] || log_weights[c] == INFINITY) {
+            set_error("component %d: log weight must be finite or -inf", c);
+            return GSSS_E_INVALID;
+        }
+    }
+    if (select_vec(d, 0) < 0) return GSSS_E_UNSUPPORTED;
+    // header (gsss_device.h, Mixture), then every component's blob as gsss_target_create packs it
+    std::vector<double> blob(1 + (size_t)n_components * kMixHeader, 0.0);
+    blob[0] = (double)n_components;
+    int64_t rows = 0, extra = 0, terms = 0;
+    int nb = 0;
+    bool curve = false;
+    double scale_all = 0.0;
+    for (int c = 0; c < n_components; ++c) {
+        const gsss_target_desc *desc = components + c;
+        std::vector<double> part;
+        bool diagonal = false;
+        double scale = 0.0;
+        int cpd_variant = 0;
+        if (int rc = pack_target(desc, part, diagonal, scale, cpd_variant)) {
+            std::string msg = g_err;
+            set_error("component %d: %s", c, msg.c_str());
+            return rc;
+        }
+        const int k = desc->kind == GSSS_BINGHAM ? ((diagonal ? 1 : 0) | (desc->mu ? 2 : 0)) : desc->k;
+        double *h = blob.data() + 1 + (size_t)c * kMixHeader;
+        h[0] = (double)desc->kind;
+        h[1] = (double)k;
+        h[2] = desc->kappa;
+        h[3] = scale;
+        h[4] = log_weights[c];
+        h[5] = (double)blob.size();
+        blob.insert(blob.end(), part.begin(), part.end());
+        scale_all = std::fmax(scale_all, scale);
+        switch (desc->kind) {
+        case GSSS_VMF_MIXTURE:
+            rows += desc->k;
+            extra += desc->k;
+            terms += desc->k;
+            break;
+        case GSSS_BINGHAM:
+            rows += d + 1;
+            ++nb;
+            ++terms;
+            break;
+        default:
+            rows += desc->k;
+            extra += 4 * (int64_t)(desc->k - 1);
+            curve = true;
+            ++terms;
+            break;
+        }
+    }
+    if (rows > kMixMaxRows || extra > kMixMaxRows) {
+        set_error("a mixture takes at most %d parameter rows in all (vMF means, knots, d + 1 per Bingham component; got %lld)",
+                  kMixMaxRows, (long long)rows);
+        return GSSS_E_UNSUPPORTED;
+    }
+    int ndev = gsss_device_count();
+    if (ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("device %d not available (%d HIP devices visible)", device, ndev);
+        return GSSS_E_NO_DEVICE;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    gsss_target *t = new (std::nothrow) gsss_target();
+    if (!t) {
+        set_error("out of host memory");
+        return GSSS_E_INVALID;
+    }
+    t->device = device;
+    t->blob_doubles = blob.size();
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), blob.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(t->blob_dev, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error("copying target parameters failed: %s", hipGetErrorString(e));
+        if (t->blob_dev) (void)hipFree(t->blob_dev);
+        delete t;
+        return GSSS_E_HIP;
+    }
+    t->tb.blob = t->blob_dev;
+    t->tb.kind = GSSS_MIXTURE;
+    t->tb.d = d;
+    t->tb.k = mix_pack_k(n_components, nb, (int)(terms < 255 ? terms : 255), curve);  // (mix_info)
+    t->tb.dpad = (int32_t)rows;
+    t->tb.kappa = (double)extra;
+    t->tb.scale = scale_all;
+    t->cpd_variant = 0;
+    *out = t;
+    return GSSS_OK;
+}
+
 int gsss_target_destroy(gsss_target *t)
 {
     if (!t) return GSSS_OK;
@@ -576,6 +727,7 @@ static int logprob_or_gradient(const gsss_target *t, const double *x_dev, int64_
     case GSSS_VMF_MIXTURE: return launch_logprob<VmfMixture>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_BINGHAM: return launch_logprob<Bingham>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_CURVE_VMF: return launch_logprob<CurveVmf>(vec, t->tb, x_dev, n, out_dev, grad, st);
+    case GSSS_MIXTURE: return launch_logprob<Mixture>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_CPD: return launch_cpd_logprob(t->cpd_variant, t->tb, x_dev, n, out_dev, grad, st);
     }
     set_error("corrupt target");
@@ -739,6 +891,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
         case GSSS_VMF_MIXTURE: return launch_mh<VmfMixture>(vec, draws, a->sampler, t->tb, rb, mb, st);
         case GSSS_BINGHAM: return launch_mh<Bingham>(vec, draws, a->sampler, t->tb, rb, mb, st);
         case GSSS_CURVE_VMF: return launch_mh<CurveVmf>(vec, draws, a->sampler, t->tb, rb, mb, st);
+        case GSSS_MIXTURE: return launch_mh<Mixture>(vec, draws, a->sampler, t->tb, rb, mb, st);
         }
         set_error("corrupt target");
         return GSSS_E_INVALID;
@@ -754,6 +907,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
     case GSSS_VMF_MIXTURE: return launch_run<VmfMixture>(vec, draws, t->tb, rb, st);
     case GSSS_BINGHAM: return launch_run<Bingham>(vec, draws, t->tb, rb, st);
     case GSSS_CURVE_VMF: return launch_run<CurveVmf>(vec, draws, t->tb, rb, st);
+    case GSSS_MIXTURE: return launch_run<Mixture>(vec, draws, t->tb, rb, st);
     }
     set_error("corrupt target");
     return GSSS_E_INVALID;
@@ -820,7 +974,10 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
         return name;
     }
     const char *vec = gsss_variant_name(t, mode, variant);
-    const char *tgt = t->tb.kind == GSSS_VMF_MIXTURE ? "VmfMixture" : (t->tb.kind == GSSS_BINGHAM ? "Bingham" : "CurveVmf");
+    const char *tgt = t->tb.kind == GSSS_VMF_MIXTURE ? "VmfMixture"
+                      : t->tb.kind == GSSS_BINGHAM   ? "Bingham"
+                      : t->tb.kind == GSSS_MIXTURE   ? "Mixture"
+                                                     : "CurveVmf";
     if (vec[0]) snprintf(name, sizeof(name), "run_kernel<%s, %s>", vec, tgt);
     return name;
 }

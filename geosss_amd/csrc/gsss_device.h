@@ -1534,6 +1534,210 @@ struct CurveVmf {
 };
 
 // ------------------------------------------------------------------------------------------
+// Mixture of the targets above (GSSS_MIXTURE; distributions.py:210-227 with any component):
+//   log_prob = logsumexp_c(log_prob_c(y) + log w_c),   gradient = sum_c softmax_c(...) gradient_c(y)
+// where every component is evaluated by its own policy (VmfMixture, Bingham, CurveVmf), unchanged.
+// Parameter blob (gsss_capi.hip, gsss_target_create_mixture): [0] the component count, then kMixHeader doubles per
+// component -- kind, k (as gsss_target_create sets TargetBlock::k), kappa, scale, log w, offset of its blob -- then the
+// components' own blobs, packed as gsss_target_create packs them.  TargetBlock: k = components | Bingham components << 5 |
+// restricted-circle terms (saturating at 255) << 10 | curve present << 18; dpad = rows of length d over all components
+// (vMF means, A rows + b, knots); kappa = the further doubles (vMF logc, curve segments).
+// LDS: the component policies (Slot) | the Bingham scratch rows | kMixDrawsReserve for the draw source | the components'
+// rows.  The policies' own sizes depend on each component's k, which TargetBlock::k cannot carry, so the rows sit behind
+// the regions the kernels address from lds_doubles(k, d); the host sizes a launch with launch_doubles().  Where the rows
+// of all components do not fit (sixty-four-lane layouts only, rows_fit_lds), every component reads them from global
+// memory as the policies do on their own, and only the Bingham linear terms stay in LDS.
+// ------------------------------------------------------------------------------------------
+constexpr int kMixMaxComponents = 16;
+constexpr int kMixMaxRows = 1 << 20;  // parameter rows of all components (TargetBlock::dpad), and their further doubles
+constexpr int kMixHeader = 8;
+constexpr int kMixDrawsReserve = 768;  // NumpyDraws<V>::kLdsDoubles, the largest draw-source table
+
+struct MixInfo {
+    int n, nb, terms;
+    bool curve;
+    int64_t rows, extra;
+};
+__host__ __device__ inline MixInfo mix_info(const TargetBlock &tb)
+{
+    MixInfo m;
+    m.n = tb.k & 31;
+    m.nb = (tb.k >> 5) & 31;
+    m.terms = (tb.k >> 10) & 255;
+    m.curve = ((tb.k >> 18) & 1) != 0;
+    m.rows = tb.dpad;
+    m.extra = (int64_t)tb.kappa;
+    return m;
+}
+__host__ __device__ constexpr int32_t mix_pack_k(int n, int nb, int terms, bool curve)
+{
+    return n | (nb << 5) | ((terms < 255 ? terms : 255) << 10) | ((curve ? 1 : 0) << 18);
+}
+
+template <class V>
+struct Mixture {
+    struct Slot {
+        int32_t kind;
+        double logw;
+        union {
+            VmfMixture<V> vm;
+            Bingham<V> bg;
+            CurveVmf<V> cv;
+        };
+    };
+    const Slot *slots;  // LDS [n]
+    int n;
+    static constexpr bool kMayGlobal = V::DPAD >= 256;  // (rows_fit_lds)
+    static constexpr int kScratchPerChain = Bingham<V>::kScratchPerChain;
+    static constexpr size_t kSlotDoubles = (sizeof(Slot) + sizeof(double) - 1) / sizeof(double);
+
+    __host__ __device__ static size_t lds_doubles(int k, int /*d*/) { return (size_t)(k & 31) * kSlotDoubles; }
+    __host__ __device__ static size_t rows_offset(const TargetBlock &tb)
+    {
+        return lds_doubles(tb.k, tb.d) + (size_t)kScratchPerChain * (kBlock / V::L) + kMixDrawsReserve;
+    }
+    // the rows of all components in LDS: always below the sixty-four-lane layouts, there while the whole launch fits
+    __host__ __device__ static bool in_lds(const TargetBlock &tb)
+    {
+        const MixInfo mi = mix_info(tb);
+        return V::DPAD < 256 || (rows_offset(tb) + (size_t)mi.rows * V::DPAD + (size_t)mi.extra) * sizeof(double) <= kMaxLdsBytes;
+    }
+    __host__ __device__ static size_t rows_doubles(const TargetBlock &tb)
+    {
+        const MixInfo mi = mix_info(tb);
+        return in_lds(tb) ? (size_t)mi.rows * V::DPAD + (size_t)mi.extra : (size_t)mi.nb * V::DPAD;
+    }
+    // the dynamic LDS of a launch (host side)
+    static size_t launch_doubles(const TargetBlock &tb) { return rows_offset(tb) + rows_doubles(tb); }
+
+    __device__ void stage(double *lds, const TargetBlock &tb)
+    {
+        n = mix_info(tb).n;
+        const bool lds_rows = in_lds(tb);
+        Slot *sl = reinterpret_cast<Slot *>(lds);
+        double *rows = lds + rows_offset(tb);
+        for (int c = 0; c < n; ++c) {
+            const double *h = tb.blob + 1 + (size_t)c * kMixHeader;
+            TargetBlock t{};
+            t.blob = tb.blob + (size_t)h[5];
+            t.kind = (int32_t)h[0];
+            t.d = tb.d;
+            t.k = (int32_t)h[1];
+            t.kappa = h[2];
+            t.scale = h[3];
+            Slot s;
+            s.kind = t.kind;
+            s.logw = h[4];
+            // in LDS: the policy's own stage() (each component alone fits where all do); else its global-memory set-up
+            if (t.kind == GSSS_VMF_MIXTURE) {
+                if (lds_rows) {
+                    s.vm.stage(rows, t);
+                    rows += VmfMixture<V>::lds_doubles(t.k, t.d);
+                } else {
+                    s.vm.K = t.k;
+                    s.vm.d = t.d;
+                    s.vm.mug = t.blob;
+                    s.vm.mu = nullptr;
+                    s.vm.logc = t.blob + (size_t)t.k * t.d;
+                }
+            } else if (t.kind == GSSS_BINGHAM) {
+                if (lds_rows) {
+                    s.bg.stage(rows, t);
+                    rows += Bingham<V>::lds_doubles(t.k, t.d);
+                } else {
+                    lds_fill(rows, 1, V::DPAD, t.blob + (size_t)t.d * t.d, t.d);
+                    s.bg.d = t.d;
+                    s.bg.A = nullptr;
+                    s.bg.Ag = t.blob;
+                    s.bg.b = rows;
+                    rows += V::DPAD;
+                }
+            } else {
+                if (lds_rows) {
+                    s.cv.stage(rows, t);
+                    rows += CurveVmf<V>::lds_doubles(t.k, t.d);
+                } else {
+                    s.cv.K = t.k;
+                    s.cv.d = t.d;
+                    s.cv.kappa = t.kappa;
+                    s.cv.knotsg = t.blob;
+                    s.cv.knots = nullptr;
+                    s.cv.seg = t.blob + (size_t)t.k * t.d;
+                }
+            }
+            if (threadIdx.x == 0) sl[c] = s;
+        }
+        slots = sl;
+    }
+    __device__ __forceinline__ double comp_logp(const Slot &s, const double (&y)[V::N], int g, double *scratch) const
+    {
+        if (s.kind == GSSS_VMF_MIXTURE) return s.vm.logp(y, g, scratch);
+        if (s.kind == GSSS_BINGHAM) return s.bg.logp(y, g, scratch);
+        return s.cv.logp(y, g, scratch);
+    }
+    __device__ __forceinline__ void comp_grad(const Slot &s, const double (&y)[V::N], int g, double *scratch, double (&out)[V::N]) const
+    {
+        if (s.kind == GSSS_VMF_MIXTURE)
+            s.vm.grad(y, g, scratch, out);
+        else if (s.kind == GSSS_BINGHAM)
+            s.bg.grad(y, g, scratch, out);
+        else
+            s.cv.grad(y, g, scratch, out);
+    }
+    // logsumexp_c( log_prob_c(y) + log w_c ), one pass with a running maximum; a zero weight (log w = -inf) adds no term
+    __device__ double logp(const double (&y)[V::N], int g, double *scratch) const
+    {
+        double m = -INFINITY, sum = 0.0;
+        bool nan = false;
+        for (int c = 0; c < n; ++c) {
+            const Slot s = slots[c];
+            if (!(s.logw > -INFINITY)) continue;
+            const double v = comp_logp(s, y, g, scratch) + s.logw;
+            if (v > m) {
+                sum = fma(sum, fm::exp_fast(m - v), 1.0);
+                m = v;
+            } else if (v > -INFINITY) {
+                sum += fm::exp_fast(v - m);
+            } else if (v != v) {
+                nan = true;
+            }
+        }
+        if (nan) return __builtin_nan("");
+        if (!(m > -INFINITY) || m == INFINITY) return m;
+        return m + fm::log_fast(sum);
+    }
+    // distributions.py:223-227 : sum_c exp(p_c) gradient_c / exp(logsumexp(p)), each gradient_c as the component's class
+    // defines it (vMF mu, Bingham and BinghamFisher 2 A y, curve kappa * nearest; Uniform(d) is a Bingham with A = 0)
+    __device__ void grad(const double (&y)[V::N], int g, double *scratch, double (&out)[V::N]) const
+    {
+        double m = -INFINITY, den = 0.0;
+#pragma unroll
+        for (int i = 0; i < V::N; ++i) out[i] = 0.0;
+        for (int c = 0; c < n; ++c) {
+            const Slot s = slots[c];
+            if (!(s.logw > -INFINITY)) continue;
+            const double v = comp_logp(s, y, g, scratch) + s.logw;
+            double gc[V::N];
+            comp_grad(s, y, g, scratch, gc);
+            if (v > m) {
+                const double r = fm::exp_fast(m - v);
+                den = fma(den, r, 1.0);
+#pragma unroll
+                for (int i = 0; i < V::N; ++i) out[i] = fma(out[i], r, gc[i]);
+                m = v;
+            } else if (v > -INFINITY) {
+                const double w = fm::exp_fast(v - m);
+                den += w;
+#pragma unroll
+                for (int i = 0; i < V::N; ++i) out[i] = fma(w, gc[i], out[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < V::N; ++i) out[i] /= den;
+    }
+};
+
+// ------------------------------------------------------------------------------------------
 // The sampler: one lane group per chain, step-synchronous.
 // ------------------------------------------------------------------------------------------
 template <class V, class T>

@@ -350,6 +350,151 @@ struct FastCurve {
     }
 };
 
+// Mixture of vMF and Bingham / Fisher-Bingham terms (GSSS_MIXTURE without a curve component; Uniform(d) is a Bingham
+// term with A = 0).  Every term k is a quadratic form on the circle plus a constant,
+//   a_k(theta) = c^2 xAx + c s (xAu + uAx) + s^2 uAu + c b.x + s b.u + L_k,
+// the vMF terms with A = 0, b = mu, L = logc + log w (the form of FastVmf), the Bingham ones with L = log w (FastBingham).
+// The accept test is FastVmf's linear one, sum_k e^{a_k(theta) - m} > U sum_k e^{a_k(x) - m} with m = max_k a_k(x).
+// A make() costs O(K d^2) (O(d) for a vMF term), a try O(K) with no d-loop.  Built for KC terms; the surplus ones are
+// skipped (the term count is wave-uniform), their LDS rows are zeros with L = kLogZero.
+template <int D, int KC>
+struct FastMixture {
+    static constexpr bool kLinear = true;
+    static constexpr int kTermDoubles = D * D + D + 1;  // A [D][D], b [D], L
+    const double *terms;  // LDS [KC][kTermDoubles]
+    struct Coef {
+        double qxx[KC], qxu[KC], quu[KC], bx[KC], bu[KC], m;
+        template <class F>
+        __device__ __forceinline__ void each(F &&f)
+        {
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                f(qxx[k]);
+                f(qxu[k]);
+                f(quu[k]);
+                f(bx[k]);
+                f(bu[k]);
+            }
+            f(m);
+        }
+    };
+    static constexpr int kCoefWords = 5 * KC + 1;
+    __host__ __device__ static size_t lds_doubles() { return (size_t)KC * kTermDoubles; }
+    int K;          // terms in use
+    uint32_t quad;  // bit k: term k is a Bingham term
+    // term k of the blob (gsss_device.h, Mixture): component c, and the inner index j of a vMF component
+    __device__ static bool find_term(const double *blob, int n, int k, int &c, int &j)
+    {
+        int t = 0;
+        for (c = 0; c < n; ++c) {
+            const double *h = blob + 1 + (size_t)c * kMixHeader;
+            const int cnt = (int)h[0] == GSSS_VMF_MIXTURE ? (int)h[1] : 1;
+            if (k < t + cnt) {
+                j = k - t;
+                return true;
+            }
+            t += cnt;
+        }
+        return false;
+    }
+    __device__ void stage(double *lds, const TargetBlock &tb)
+    {
+        const MixInfo mi = mix_info(tb);
+        K = mi.terms < KC ? mi.terms : KC;
+        quad = 0u;
+        for (int k = 0; k < K; ++k) {
+            int c, j;
+            if (find_term(tb.blob, mi.n, k, c, j) && (int)tb.blob[1 + (size_t)c * kMixHeader] == GSSS_BINGHAM) quad |= 1u << k;
+        }
+        // one thread per term fills its row
+        for (int k = threadIdx.x; k < KC; k += kBlock) {
+            double *row = lds + (size_t)k * kTermDoubles;
+            for (int i = 0; i < kTermDoubles; ++i) row[i] = 0.0;
+            row[D * D + D] = kLogZero;
+            int c, j;
+            if (k >= K || !find_term(tb.blob, mi.n, k, c, j)) continue;
+            const double *h = tb.blob + 1 + (size_t)c * kMixHeader;
+            const double *cb = tb.blob + (size_t)h[5];
+            const int kc = (int)h[1];
+            if ((int)h[0] == GSSS_BINGHAM) {
+                for (int i = 0; i < D * D + D; ++i) row[i] = cb[i];  // A rows, then b (zeros for a plain Bingham)
+                row[D * D + D] = fmax(h[4], kLogZero);
+            } else {
+                for (int i = 0; i < D; ++i) row[D * D + i] = cb[(size_t)j * D + i];
+                // a zero weight has L = -inf (log w_k, distributions.py:220): e^{-1e5} is as much a zero, and stays finite
+                row[D * D + D] = fmax(cb[(size_t)kc * D + j] + h[4], kLogZero);
+            }
+        }
+        terms = lds;
+    }
+    __device__ __forceinline__ double make(Coef &cf, const double (&x)[D], const double (&u)[D], double /*lvl*/,
+                                           bool /*fresh*/) const
+    {
+        double m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            double qxx = 0.0, qxu = 0.0, quu = 0.0, bx = 0.0, bu = 0.0;
+            if (k < K) {
+                const double *A = terms + (size_t)k * kTermDoubles, *b = A + D * D;
+                if ((quad >> k) & 1u) {
+#pragma unroll
+                    for (int jj = 0; jj < D; ++jj) {
+                        double xa = 0.0, ua = 0.0;  // (x A)_j, (u A)_j (distributions.py:86 contracts rows first)
+#pragma unroll
+                        for (int i = 0; i < D; ++i) {
+                            const double aij = A[i * D + jj];
+                            xa = fma(x[i], aij, xa);
+                            ua = fma(u[i], aij, ua);
+                        }
+                        qxx = fma(xa, x[jj], qxx);
+                        qxu = fma(xa, u[jj], fma(ua, x[jj], qxu));
+                        quu = fma(ua, u[jj], quu);
+                        if constexpr (D > 10) __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+#pragma unroll
+                for (int jj = 0; jj < D; ++jj) {
+                    bx = fma(b[jj], x[jj], bx);
+                    bu = fma(b[jj], u[jj], bu);
+                }
+                m = fmax(m, (qxx + bx) + b[D]);
+            }
+            cf.qxx[k] = qxx;
+            cf.qxu[k] = qxu;
+            cf.quu[k] = quu;
+            cf.bx[k] = bx;
+            cf.bu[k] = bu;
+        }
+        // level of x itself, computed from x as the reference forms its threshold (mcmc.py:389); m only keeps the
+        // exponentials in range
+        cf.m = m;
+        double lvl = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k)
+            if (k < K) lvl += fm::exp_fast(((cf.qxx[k] + cf.bx[k]) + terms[(size_t)k * kTermDoubles + D * D + D]) - m);
+        return lvl;
+    }
+    __device__ __forceinline__ double level(const Coef &cf, double c, double s) const
+    {
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            if (k < K) {
+                const double L = terms[(size_t)k * kTermDoubles + D * D + D];
+                double a;
+                if ((quad >> k) & 1u)
+                    a = fma(c * c, cf.qxx[k], fma(c * s, cf.qxu[k], (s * s) * cf.quu[k])) + fma(c, cf.bx[k], fma(s, cf.bu[k], L));
+                else
+                    a = fma(c, cf.bx[k], fma(s, cf.bu[k], L));
+                // (exp_fast's clamp: a Bingham term may rise far above the level of x along the circle -- +inf, an accept)
+                sum += fm::exp_fast(a - cf.m);
+            }
+        }
+        return sum;
+    }
+    __device__ __forceinline__ double level(const Coef &cf, double c, double s, double /*thr*/) const { return level(cf, c, s); }
+};
+
 // ------------------------------------------------------------------------------------------
 // per-chain state: only what must survive between tries.  RNG counters are rebuilt from
 // (id, steps_done, t) when a draw is needed.  A lane keeps its current chain in registers and
@@ -767,6 +912,7 @@ struct FastProbe {
 int launch_fast_vmf(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
 int launch_fast_bingham(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
 int launch_fast_curve(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
+int launch_fast_mixture(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
 int launch_curvespec(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, bool lane, hipStream_t st);
 #define GSSS_PROBE(LANE, ...)                                         \
     do {                                                              \

@@ -2,7 +2,8 @@
 geosss/distributions.py for the families the hot path covers:
 
     VonMisesFisher(mu)                      distributions.py:117-160
-    MixtureModel(components, weights=None)  distributions.py:209-227
+    MixtureModel(components, weights=None)  distributions.py:209-227 (components: vMF, Bingham, BinghamFisher,
+                                            Uniform, CurvedVonMisesFisher, MixtureModel)
     Bingham(A), random_bingham(...)         distributions.py:36-103, 230-258
     CurvedVonMisesFisher(curve, kappa)      distributions.py:261-278
     SlerpCurve(knots), brownian_curve(...)  spherical_curve.py:74-129
@@ -71,6 +72,19 @@ class _DeviceTarget:
         self.lib = _lib.load()
         self.device = device
         self._keep = (desc_arrays, extra)  # keep the host arrays alive during create
+        if kind == _lib.MIXTURE:  # extra: the components' packs and their log weights (MixtureModel._pack)
+            comps = extra["components"]
+            descs = (_lib.TargetDesc * len(comps))()
+            for i, (ckind, cd, ck, ckappa, arrays) in enumerate(comps):
+                descs[i] = _lib.TargetDesc(ckind, cd, ck, 0,
+                                           *[a.ctypes.data_as(C.c_void_p) if a is not None else None for a in arrays],
+                                           float(ckappa))
+            logw = extra["log_weights"]
+            h = C.c_void_p()
+            _lib.check(self.lib.gsss_target_create_mixture(descs, len(comps), logw.ctypes.data_as(C.c_void_p), device,
+                                                           C.byref(h)))
+            self.handle = h
+            return
         desc = _lib.TargetDesc(kind, d, k, 0,
                                *[a.ctypes.data_as(C.c_void_p) if a is not None else None for a in desc_arrays],
                                float(kappa))
@@ -95,24 +109,34 @@ class Distribution:
     def _pack(self):
         """-> (kind, d, k, kappa, (mu, logc, A, knots))"""
         raise TypeError(f"{type(self).__name__} has no device parameter block: the samplers run inside HIP kernels and cannot call a "
-                        "Python log_prob; built-in targets are VonMisesFisher, MixtureModel (of vMF components), Bingham, "
-                        "BinghamFisher, CurvedVonMisesFisher, Uniform, CoherentPointDrift and GaussianMixtureModel")
+                        "Python log_prob; built-in targets are VonMisesFisher, Bingham, BinghamFisher, CurvedVonMisesFisher, "
+                        "Uniform, MixtureModel (of any of these), CoherentPointDrift and GaussianMixtureModel")
 
     def _device_target(self, device=None):
         dev = _device_index(device)
         packed = self._pack()
         kind, d, k, kappa, arrays = packed[:5]
         extra = packed[5] if len(packed) > 5 else None
-        # the parameter attributes are public and mutable, as in the reference: key the device copy on
-        # their current bytes so that an edited target is re-uploaded instead of silently reused
-        key = (kind, d, k, kappa) + tuple(a.tobytes() if a is not None else None for a in arrays)
-        if extra:
-            key += tuple(v.tobytes() if isinstance(v, np.ndarray) else v for v in extra.values())
+        key = self._device_key(packed)
         cache = self.__dict__.setdefault("_targets", {})
         hit = cache.get(dev)
         if hit is None or hit[0] != key:
             cache[dev] = (key, _DeviceTarget(arrays, kind, d, k, kappa, dev, extra))
         return cache[dev][1]
+
+    @staticmethod
+    def _device_key(packed):
+        # the parameter attributes are public and mutable, as in the reference: key the device copy on
+        # their current bytes so that an edited target is re-uploaded instead of silently reused
+        kind, d, k, kappa, arrays = packed[:5]
+        extra = packed[5] if len(packed) > 5 else None
+        key = (kind, d, k, kappa) + tuple(a.tobytes() if a is not None else None for a in arrays)
+        if extra and kind == _lib.MIXTURE:  # every component's parameter bytes: editing pdfs[1].A re-uploads
+            key += tuple((c[:4],) + tuple(a.tobytes() if a is not None else None for a in c[4]) for c in extra["components"])
+            key += (extra["log_weights"].tobytes(),)
+        elif extra:
+            key += tuple(v.tobytes() if isinstance(v, np.ndarray) else v for v in extra.values())
+        return key
 
     def _invalidate(self):
         self.__dict__.pop("_targets", None)
@@ -220,8 +244,8 @@ class _HostDensity(Distribution):
 
     def _pack(self):
         raise TypeError(f"{type(self).__name__} is a host-side density (plotting / envelope); the HIP samplers run on "
-                        "VonMisesFisher, MixtureModel, Bingham, BinghamFisher, CurvedVonMisesFisher, Uniform and the "
-                        "registration targets")
+                        "VonMisesFisher, Bingham, BinghamFisher, CurvedVonMisesFisher, Uniform, MixtureModel (of any of these) "
+                        "and the registration targets")
 
 
 class MarginalVonMisesFisher(_HostDensity, VonMisesFisher):
@@ -278,19 +302,34 @@ class ACG(MultivariateNormal):
 
 
 class MixtureModel(Distribution):
-    """log_prob = logsumexp_k(log_prob_k(x) + log w_k), weights normalised to one
-    (distributions.py:211-221).  Components must be VonMisesFisher of one dimension."""
+    """log_prob = logsumexp_k(log_prob_k(x) + log w_k), weights normalised to one (distributions.py:211-221);
+    gradient = the softmax-weighted sum of the components' gradients (:223-227).
+
+    Components: VonMisesFisher, Bingham, BinghamFisher, Uniform, CurvedVonMisesFisher and MixtureModel, of one dimension.  A
+    nested mixture is flattened (its weights multiply the parent's, its components become terms); a dimensionless Uniform()
+    takes the dimension of its siblings, the reference's way of writing an outlier background.  A mixture of vMF terms only
+    runs on the vMF-mixture kernels as before; any other runs on the GSSS_MIXTURE kernels.  log_prob and gradient are
+    evaluated on the device for a point (d,), rows (n, d) or a CUDA tensor -- rows also with a Uniform component, which the
+    reference's batched call does not take.  `log_prob.num_calls` counts the mixture's evaluations as for every target; the
+    component objects' own counters do not advance."""
 
     def __init__(self, components, weights=None):
         self.pdfs = list(components)
-        if not self.pdfs or not all(isinstance(p, VonMisesFisher) for p in self.pdfs):
-            raise TypeError("the HIP path covers mixtures of VonMisesFisher components")
+        if not self.pdfs:
+            raise TypeError("a mixture needs at least one component")
         # a mixture of coordinate marginals (the reference's histogram overlay, scripts/vMF_diagnostics.py:106-108) is a
         # density on [-1, 1]: host arithmetic, never a sampler target
         self._marginal = all(isinstance(p, MarginalVonMisesFisher) for p in self.pdfs)
         if not self._marginal and any(isinstance(p, MarginalVonMisesFisher) for p in self.pdfs):
             raise TypeError("cannot mix coordinate marginals with densities on the sphere")
-        if len({p.d for p in self.pdfs}) != 1:
+        if not self._marginal:
+            for p in self.pdfs:
+                if isinstance(p, _HostDensity) or not isinstance(p, (VonMisesFisher, Bingham, CurvedVonMisesFisher, MixtureModel)):
+                    raise TypeError(f"{type(p).__name__} is not a mixture component on the device: components are VonMisesFisher, "
+                                    "Bingham, BinghamFisher, Uniform, CurvedVonMisesFisher and MixtureModel")
+                if isinstance(p, MixtureModel) and p._marginal:
+                    raise TypeError("cannot mix coordinate marginals with densities on the sphere")
+        if len({p.d for p in self.pdfs if p.d is not None}) > 1:
             raise ValueError("all components must share the dimension")
         w = np.ones(len(self.pdfs)) if weights is None else np.array(weights, dtype=np.float64)
         if w.shape != (len(self.pdfs),):
@@ -299,16 +338,55 @@ class MixtureModel(Distribution):
 
     @property
     def d(self):
-        return self.pdfs[0].d
+        for p in self.pdfs:
+            if p.d is not None:
+                return p.d
+        return None
+
+    def _terms(self, d=None):
+        """The flattened mixture: [(component, weight)], nested mixtures expanded, Uniform() given the dimension d."""
+        d = self.d if d is None else d
+        out = []
+        for p, w in zip(self.pdfs, self.weights):
+            if isinstance(p, MixtureModel):
+                out += [(q, w * v) for q, v in p._terms(d)]
+            elif isinstance(p, Uniform) and p.d is None and d is not None:
+                out.append((Uniform(d), w))
+            else:
+                out.append((p, w))
+        return out
+
+    def _modes(self):
+        """Mode directions of the terms that have one (the running statistics' mode occupancy): a vMF term's mu, a Bingham
+        term's .mode; Uniform and curve terms have none."""
+        return [p.mu if isinstance(p, VonMisesFisher) else p.mode for p, _ in self._terms()
+                if isinstance(p, VonMisesFisher) or (isinstance(p, Bingham) and not isinstance(p, Uniform))]
 
     def _pack(self):
         if self._marginal:
             return _HostDensity._pack(self)
-        mu = _as_f64([p.mu for p in self.pdfs])
+        if self.d is None:
+            raise TypeError("a mixture of Uniform() components has no dimension: give one as Uniform(d)")
+        terms = self._terms()
         with np.errstate(divide="ignore"):
-            logw = np.log(self.weights)
-        logc = _as_f64([p._log_const() for p in self.pdfs]) + logw
-        return _lib.VMF_MIXTURE, self.d, len(self.pdfs), 0.0, (mu, _as_f64(logc), None, None)
+            logw = np.log(np.array([w for _, w in terms], dtype=np.float64))
+        vmf = [i for i, (p, _) in enumerate(terms) if isinstance(p, VonMisesFisher)]
+        if len(vmf) == len(terms):  # vMF terms only: the vMF-mixture target, with the arrays it has always had
+            mu = _as_f64([p.mu for p, _ in terms])
+            logc = _as_f64([p._log_const() for p, _ in terms]) + logw
+            return _lib.VMF_MIXTURE, self.d, len(terms), 0.0, (mu, _as_f64(logc), None, None)
+        # GSSS_MIXTURE: the vMF terms as one vMF-mixture component (their weights inside logc), the others one each
+        comps, cw = [], []
+        if vmf:
+            mu = _as_f64([terms[i][0].mu for i in vmf])
+            logc = _as_f64([terms[i][0]._log_const() for i in vmf]) + logw[vmf]
+            comps.append((_lib.VMF_MIXTURE, self.d, len(vmf), 0.0, (mu, _as_f64(logc), None, None)))
+            cw.append(0.0)
+        for (p, _), lw in zip(terms, logw):
+            if not isinstance(p, VonMisesFisher):
+                comps.append(tuple(p._pack()[:5]))
+                cw.append(lw)
+        return _lib.MIXTURE, self.d, len(comps), 0.0, (), {"components": comps, "log_weights": _as_f64(cw)}
 
     @counted
     def log_prob(self, x):
@@ -319,7 +397,7 @@ class MixtureModel(Distribution):
 
     @counted
     def gradient(self, x):
-        """The softmax-weighted mean of the components' gradients (distributions.py:223-227), on the device."""
+        """The softmax-weighted sum of the components' gradients (distributions.py:223-227), on the device."""
         if self._marginal:
             return _HostDensity._pack(self)
         return self._gradient_device(x)

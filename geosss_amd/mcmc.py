@@ -205,7 +205,8 @@ class RejectionSphericalSliceSampler:
         (utils.py:96-110) and its IAT / n_eff heuristic (:119-134) follow -- without storing a single draw.
         Statistics are taken at the cadence of `advance(..., thin=t)` (every t-th state), like diagnostics computed
         from a thinned stored chain.  Defaults: projection = first coordinate; hop = the target's `.mode` if it has
-        one; modes = the component means of a MixtureModel.  second_moment: keep the d (d + 1) / 2 sums of x_i x_j too
+        one; modes = the mode directions of a MixtureModel's terms (a vMF term's mu, a Bingham term's .mode; terms without
+        a mode are left out).  second_moment: keep the d (d + 1) / 2 sums of x_i x_j too
         (default: for d <= 16; they grow as d^2 -- 20 100 rows per chain at d = 200).  Every slice-sampler kernel family
         accumulates them (lane, lane-group and cooperative layouts)."""
         d = self.d
@@ -217,7 +218,7 @@ class RejectionSphericalSliceSampler:
             hop = np.zeros(d) if hop is None or np.ndim(hop) != 1 else hop
         if modes is None:
             pdfs = getattr(self.target, "pdfs", None)
-            modes = np.array([p.mu for p in pdfs]) if pdfs else np.zeros((0, d))
+            modes = np.array(self.target._modes()) if pdfs else np.zeros((0, d))
         modes = np.asarray(modes, dtype=np.float64).reshape(-1, d)
         dirs = np.concatenate([w[None], np.asarray(hop, dtype=np.float64)[None], modes], axis=0)
         if dirs.shape[1] != d:

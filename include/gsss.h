@@ -39,6 +39,10 @@ extern "C" {
 #define GSSS_BINGHAM 2     /* Bingham                         :36-103            */
 #define GSSS_CURVE_VMF 3   /* CurvedVonMisesFisher+SlerpCurve :261-278, spherical_curve.py:10-32,74-102 */
 #define GSSS_CPD 4         /* registration.py: CoherentPointDrift :186-293 / GaussianMixtureModel :62-118 on unit quaternions (d = 4) */
+#define GSSS_MIXTURE 5     /* MixtureModel of any components :209-227 -- made by gsss_target_create_mixture, never by gsss_target_create:
+                              logsumexp_c(log_prob_c + log w_c); components GSSS_VMF_MIXTURE, GSSS_BINGHAM (with or without b) or
+                              GSSS_CURVE_VMF of one d, at most 16 of them and 2^20 parameter rows in all (vMF means, knots, d + 1 per
+                              Bingham).  Fast mode: d = 3 .. 16, at most 8 vMF / Bingham terms, no curve component. */
 
 /* samplers (geosss/mcmc.py) */
 #define GSSS_SHRINK 0 /* ShrinkageSphericalSliceSampler.__next__  :382-401 */
@@ -234,6 +238,13 @@ int gsss_device_count(void);
 
 /* distributions.py ctor twins: copy the parameters to `device` */
 int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **out);
+/* MixtureModel(components, weights) with any of the kinds above as components (GSSS_MIXTURE): each component an ordinary
+ * descriptor of kind GSSS_VMF_MIXTURE, GSSS_BINGHAM or GSSS_CURVE_VMF, all of one d; log_weights[c] = log w_c, -inf for a zero
+ * weight.  Nested mixtures are flattened by the caller.  GSSS_E_INVALID: components of different d, an unknown kind or a NaN /
+ * +inf weight; GSSS_E_UNSUPPORTED: a GSSS_CPD component, more than 16 components or 2^20 parameter rows (gsss_last_error says
+ * which).  The handle serves every call a target handle serves. */
+int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_components, const double *log_weights, int device,
+                               gsss_target **out);
 int gsss_target_destroy(gsss_target *t);
 int gsss_target_dim(const gsss_target *t);
 
