@@ -17,9 +17,10 @@ from .rand import sample_bingham, sample_bingham_2d, sample_bingham_3d, sample_v
 from .registration import CoherentPointDrift, GaussianMixtureModel, PointCloud, RotationMatrix, RotationProjection
 from .sphere import (cartesian2polar, cartesian2spherical, givens, orthogonal_projection, polar2cartesian, radial_projection,
                      sample_sphere, sample_sphere_device, sample_subsphere, spherical2cartesian, spherical_projection)
+from .usertarget import DeviceDistribution
 from .utils import SamplerLauncher, colors, count_calls, counter, take_time
 
-__all__ = ["Bingham", "BinghamFisher", "CurvedVonMisesFisher", "Distribution", "MixtureModel", "SlerpCurve", "VonMisesFisher",
+__all__ = ["Bingham", "BinghamFisher", "CurvedVonMisesFisher", "DeviceDistribution", "Distribution", "MixtureModel", "SlerpCurve", "VonMisesFisher",
            "brownian_curve", "random_bingham", "RejectionSphericalSliceSampler", "ShrinkageSphericalSliceSampler",
            "MetropolisHastings", "SphericalHMC", "IndependenceSampler", "MixtureRWMHIndependenceSampler", "determine_burnin", "sample_sphere", "sample_sphere_device", "SamplerLauncher", "count_calls", "counter", "take_time",
            "sphere", "diagnostics", "registration", "rand", "sample_vMF", "sample_bingham", "sample_bingham_2d", "sample_bingham_3d", "CoherentPointDrift", "GaussianMixtureModel", "PointCloud", "RotationProjection", "IAT", "acf", "acf_fft", "distance", "n_eff",

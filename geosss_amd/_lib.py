@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSSS_HIP_LIB") or os.path.join(_HERE, "libgsss_hip.so")  # env: side-by-side A/B builds
 
-VMF_MIXTURE, BINGHAM, CURVE_VMF, CPD, MIXTURE = 1, 2, 3, 4, 5
+VMF_MIXTURE, BINGHAM, CURVE_VMF, CPD, MIXTURE, USER = 1, 2, 3, 4, 5, 6
 SHRINK, REJECT, RWMH, HMC, INDEP, MIX = 0, 1, 2, 3, 4, 5
 MODE_EXACT, MODE_FAST = 0, 1
 VARIANT_FAST_DOUBLE = 100
@@ -52,6 +52,8 @@ SIGNATURES = {
     "gsss_device_count": (C.c_int, []),
     "gsss_target_create": (C.c_int, [C.POINTER(TargetDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "gsss_target_create_mixture": (C.c_int, [C.POINTER(TargetDesc), C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "gsss_exact_layout": (C.c_int, [C.c_int32]),
+    "gsss_target_create_user": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gsss_target_destroy": (C.c_int, [C.c_void_p]),
     "gsss_target_dim": (C.c_int, [C.c_void_p]),
     "gsss_logprob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

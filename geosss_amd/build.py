@@ -54,8 +54,12 @@ def hipcc():
     return exe
 
 
+# the translation unit of a user-defined target: compiled per target by geosss_amd/usertarget.py, not into the library
+USER_MODULE = "gsss_user_module.hip"
+
+
 def sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and f != USER_MODULE)
 
 
 def headers_mtime():

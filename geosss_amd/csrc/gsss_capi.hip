@@ -12,6 +12,7 @@
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
+#include "gsss_user_target.h"
 
 namespace gsss {
 
@@ -396,6 +397,7 @@ struct gsss_target {
     double *blob_dev;
     size_t blob_doubles;
     int cpd_variant;  // GSSS_CPD: which registration kernel (neighbour-list size, uniform source weights)
+    const UserModuleTable *user;  // GSSS_USER: the compiled module's launchers (gsss_user_target.h)
 };
 
 // The parameter blob of one target (layout per kind: TargetBlock::blob); gsss_target_create, and per component
@@ -700,6 +702,83 @@ int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_com
     return GSSS_OK;
 }
 
+int gsss_exact_layout(int32_t d)
+{
+    if (d < 2) {
+        set_error("d must be >= 2 (got %d)", d);
+        return GSSS_E_INVALID;
+    }
+    return select_vec(d, 0);
+}
+
+int gsss_target_create_user(const void *table, int32_t d, const double *params, int64_t n_params, int device, gsss_target **out)
+{
+    if (!table || !out || n_params < 0 || (n_params > 0 && !params)) {
+        set_error("bad argument to gsss_target_create_user");
+        return GSSS_E_INVALID;
+    }
+    *out = nullptr;
+    const UserModuleTable *m = static_cast<const UserModuleTable *>(table);
+    if (m->module_abi != kUserModuleAbi || m->gsss_abi != GSSS_ABI_VERSION) {
+        set_error("user module built for module ABI %d / library ABI %d, this library has %d / %d: recompile it", m->module_abi,
+                  m->gsss_abi, kUserModuleAbi, GSSS_ABI_VERSION);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (!m->digest || strcmp(m->digest, gsss_source_digest()) != 0) {
+        set_error("user module compiled from other kernel sources (digest %.12s) than this library (%.12s): recompile it",
+                  m->digest ? m->digest : "none", gsss_source_digest());
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (d < 2) {
+        set_error("d must be >= 2 (got %d)", d);
+        return GSSS_E_INVALID;
+    }
+    const int vec = select_vec(d, 0);
+    if (vec < 0) return vec;
+    if (vec != m->vec_id) {
+        set_error("user module built for vector layout %d, d=%d runs in layout %d", m->vec_id, d, vec);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (n_params > 0x7FFFFFFFll) {
+        set_error("a user target takes at most 2^31-1 parameters");
+        return GSSS_E_UNSUPPORTED;
+    }
+    int ndev = gsss_device_count();
+    if (ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("device %d not available (%d HIP devices visible)", device, ndev);
+        return GSSS_E_NO_DEVICE;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    gsss_target *t = new (std::nothrow) gsss_target();
+    if (!t) {
+        set_error("out of host memory");
+        return GSSS_E_INVALID;
+    }
+    t->device = device;
+    t->blob_doubles = (size_t)n_params;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), (n_params > 0 ? (size_t)n_params : 1) * sizeof(double));
+    if (e == hipSuccess && n_params > 0)
+        e = hipMemcpy(t->blob_dev, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error("copying target parameters failed: %s", hipGetErrorString(e));
+        if (t->blob_dev) (void)hipFree(t->blob_dev);
+        delete t;
+        return GSSS_E_HIP;
+    }
+    t->tb.blob = t->blob_dev;
+    t->tb.kind = GSSS_USER;
+    t->tb.d = d;
+    t->tb.k = (int32_t)n_params;
+    t->tb.dpad = 0;
+    t->tb.kappa = 0.0;
+    t->tb.scale = 0.0;
+    t->cpd_variant = 0;
+    t->user = m;
+    *out = t;
+    return GSSS_OK;
+}
+
 int gsss_target_destroy(gsss_target *t)
 {
     if (!t) return GSSS_OK;
@@ -729,6 +808,12 @@ static int logprob_or_gradient(const gsss_target *t, const double *x_dev, int64_
     case GSSS_CURVE_VMF: return launch_logprob<CurveVmf>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_MIXTURE: return launch_logprob<Mixture>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_CPD: return launch_cpd_logprob(t->cpd_variant, t->tb, x_dev, n, out_dev, grad, st);
+    case GSSS_USER:
+        if (grad && !t->user->has_gradient) {
+            set_error("this user target defines no gsss_user_gradient");
+            return GSSS_E_UNSUPPORTED;
+        }
+        return t->user->logprob(t->tb, x_dev, n, out_dev, grad, st);
     }
     set_error("corrupt target");
     return GSSS_E_INVALID;
@@ -791,12 +876,20 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
         set_error("replay_stride must be >= 1");
         return GSSS_E_INVALID;
     }
+    if (t->tb.kind == GSSS_USER && a->mode == GSSS_MODE_FAST) {
+        set_error("fast mode is not built for user targets (GSSS_USER): use GSSS_MODE_EXACT");
+        return GSSS_E_UNSUPPORTED;
+    }
     if (a->mode == GSSS_MODE_FAST && a->variant != 0 && a->variant != GSSS_VARIANT_FAST_DOUBLE && a->variant != GSSS_VARIANT_FAST_VERIFY) {
         set_error("fast mode takes variant 0, GSSS_VARIANT_FAST_DOUBLE or GSSS_VARIANT_FAST_VERIFY");
         return GSSS_E_INVALID;
     }
     const int vec = a->mode == GSSS_MODE_FAST ? 0 : select_vec_for(t->tb, a->variant);
     if (vec < 0) return vec;
+    if (t->tb.kind == GSSS_USER && vec != t->user->vec_id) {
+        set_error("user module is built for vector layout %d only (variant %d asked for)", t->user->vec_id, a->variant);
+        return GSSS_E_UNSUPPORTED;
+    }
     RunBlock rb{};
     rb.state = a->state_dev;
     rb.samples = a->samples_dev;
@@ -887,6 +980,13 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
         mb.momenta_samples = a->sampler == GSSS_HMC ? a->momenta_samples_dev : nullptr;
         mb.stepsize_trace = a->sampler == GSSS_HMC ? nullptr : a->stepsize_trace_dev;
         if (t->tb.kind == GSSS_CPD) return launch_cpd_mh(t->cpd_variant, draws, a->sampler, t->tb, rb, mb, st);
+        if (t->tb.kind == GSSS_USER) {
+            if (a->sampler == GSSS_HMC && !t->user->has_gradient) {
+                set_error("spherical HMC needs the target's gradient: this user target defines no gsss_user_gradient");
+                return GSSS_E_UNSUPPORTED;
+            }
+            return t->user->mh(draws, a->sampler, t->tb, rb, mb, st);
+        }
         switch (t->tb.kind) {
         case GSSS_VMF_MIXTURE: return launch_mh<VmfMixture>(vec, draws, a->sampler, t->tb, rb, mb, st);
         case GSSS_BINGHAM: return launch_mh<Bingham>(vec, draws, a->sampler, t->tb, rb, mb, st);
@@ -908,6 +1008,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
     case GSSS_BINGHAM: return launch_run<Bingham>(vec, draws, t->tb, rb, st);
     case GSSS_CURVE_VMF: return launch_run<CurveVmf>(vec, draws, t->tb, rb, st);
     case GSSS_MIXTURE: return launch_run<Mixture>(vec, draws, t->tb, rb, st);
+    case GSSS_USER: return t->user->run(draws, t->tb, rb, st);
     }
     set_error("corrupt target");
     return GSSS_E_INVALID;
@@ -977,6 +1078,7 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
     const char *tgt = t->tb.kind == GSSS_VMF_MIXTURE ? "VmfMixture"
                       : t->tb.kind == GSSS_BINGHAM   ? "Bingham"
                       : t->tb.kind == GSSS_MIXTURE   ? "Mixture"
+                      : t->tb.kind == GSSS_USER      ? "UserTarget"
                                                      : "CurveVmf";
     if (vec[0]) snprintf(name, sizeof(name), "run_kernel<%s, %s>", vec, tgt);
     return name;

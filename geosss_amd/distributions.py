@@ -85,6 +85,13 @@ class _DeviceTarget:
                                                            C.byref(h)))
             self.handle = h
             return
+        if kind == _lib.USER:  # extra: the compiled module's table (usertarget.DeviceDistribution._pack)
+            (p,) = desc_arrays
+            h = C.c_void_p()
+            _lib.check(self.lib.gsss_target_create_user(C.c_void_p(extra["table"]), d, p.ctypes.data_as(C.c_void_p) if p.size else None,
+                                                        p.size, device, C.byref(h)))
+            self.handle = h
+            return
         desc = _lib.TargetDesc(kind, d, k, 0,
                                *[a.ctypes.data_as(C.c_void_p) if a is not None else None for a in desc_arrays],
                                float(kappa))
@@ -324,6 +331,9 @@ class MixtureModel(Distribution):
             raise TypeError("cannot mix coordinate marginals with densities on the sphere")
         if not self._marginal:
             for p in self.pdfs:
+                if getattr(p, "_device_source", False):
+                    raise TypeError("a DeviceDistribution is not a mixture component on the device: write the mixture in its "
+                                    "source instead")
                 if isinstance(p, _HostDensity) or not isinstance(p, (VonMisesFisher, Bingham, CurvedVonMisesFisher, MixtureModel)):
                     raise TypeError(f"{type(p).__name__} is not a mixture component on the device: components are VonMisesFisher, "
                                     "Bingham, BinghamFisher, Uniform, CurvedVonMisesFisher and MixtureModel")

@@ -832,6 +832,9 @@ class SphericalHMC(MetropolisHastings):
     _sampler = _lib.HMC
 
     def __init__(self, distribution, initial_state, seed=None, stepsize=1e-3, n_steps=10, **kwargs):
+        if getattr(distribution, "_device_source", False) and not distribution.has_gradient:
+            raise ValueError("SphericalHMC needs the target's gradient: this DeviceDistribution's source defines no "
+                             "gsss_user_gradient")
         super().__init__(distribution, initial_state, seed, stepsize=stepsize, **kwargs)
         self.n_steps = int(n_steps)
         if self.n_steps < 1:

@@ -43,6 +43,9 @@ extern "C" {
                               logsumexp_c(log_prob_c + log w_c); components GSSS_VMF_MIXTURE, GSSS_BINGHAM (with or without b) or
                               GSSS_CURVE_VMF of one d, at most 16 of them and 2^20 parameter rows in all (vMF means, knots, d + 1 per
                               Bingham).  Fast mode: d = 3 .. 16, at most 8 vMF / Bingham terms, no curve component. */
+#define GSSS_USER 6        /* a density the user writes in C++ (Distribution subclassed, distributions.py:16-25), compiled into a module of
+                              its own for ONE vector layout and made by gsss_target_create_user, never by gsss_target_create.
+                              GSSS_MODE_EXACT only; no mixture component. */
 
 /* samplers (geosss/mcmc.py) */
 #define GSSS_SHRINK 0 /* ShrinkageSphericalSliceSampler.__next__  :382-401 */
@@ -245,6 +248,16 @@ int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **o
  * which).  The handle serves every call a target handle serves. */
 int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_components, const double *log_weights, int device,
                                gsss_target **out);
+/* The vector layout (an id of gsss_variant_name's list) the exact kernels run dimension d in: the layout a user module for d must
+ * be compiled for (geosss_amd/usertarget.py passes it as -DGSSS_USER_VEC).  < 0: no layout covers d. */
+int gsss_exact_layout(int32_t d);
+/* A user-defined target (GSSS_USER).  `table` is what the compiled module's one export, gsss_user_module_table, returns: its
+ * launchers (geosss_amd/csrc/gsss_user_target.h); the module is linked against this library and must stay loaded while the handle
+ * lives.  params[n_params] are copied to `device` and handed, read-only, to the module's gsss_user_log_prob / gsss_user_gradient.
+ * GSSS_E_UNSUPPORTED (with the reason in gsss_last_error): a module built against another ABI or from other kernel sources than
+ * this library (gsss_source_digest), or for another layout than gsss_exact_layout(d).  gsss_run then takes GSSS_MODE_EXACT only
+ * and no other variant than that layout; gsss_gradient and GSSS_HMC need a module with a gradient. */
+int gsss_target_create_user(const void *table, int32_t d, const double *params, int64_t n_params, int device, gsss_target **out);
 int gsss_target_destroy(gsss_target *t);
 int gsss_target_dim(const gsss_target *t);
 
