@@ -162,8 +162,9 @@ struct ScreenVmf : FastVmf<D, KC> {
         for (int k = 0; k < KC; ++k) {
             q[2 * KC + k] -= t2;
             // (padding components beyond K have exponent -1e5: they add +0 to every sum and carry no error)
-            if (k < this->K) b = fmaxf(b, fabsf(q[k]) + fabsf(q[KC + k]) + fabsf(q[2 * KC + k]) + fabsf(t2));
+            if (k < this->K) b = fmaxf(b, fabsf(q[k]) + fabsf(q[KC + k]) + fabsf(q[2 * KC + k]));
         }
+        b += fabsf(t2);  // = max_k (... + |t2|) bit for bit: rounding is monotone and every term is >= 0
         // error of one exponent of a try: (|ax| + |au|) (eps_sincos + 2^-24) + |lc| 2^-24 + two fma roundings, plus the
         // error of log2 thr: three roundings per exponent of s0, v_exp_f32, the additions, v_log_f32 twice, the subtraction
         const float e_a = b * (kSinCosErr32 + 7.0f * kUnit32) + (1.4427f * (kExp2Err32 + (float)KC * kUnit32) + 6.0e-8f + kLog2Err32);
@@ -184,19 +185,30 @@ struct ScreenVmf : FastVmf<D, KC> {
         // instructions; K = 10: 58.4 -> 56.4 ms.  At K = 3 the moves that pair the operands cost more: 28.0 -> 29.6 ms)
         typedef float f2 __attribute__((ext_vector_type(2)));
         const f2 c2 = {c, c}, s2 = {s, s};
-        float sum = 0.0f;
+        // the sum starts at its first term, not at 0 + it: the same value (v_exp_f32 gives +0 at the least, or NaN), one
+        // instruction less a try -- the compiler may not drop the addition itself (0 + -0 would be +0)
+        float sum;
         constexpr int kPacked = KC >= 6 ? KC - KC % 2 : 0;
 #pragma unroll
         for (int k = 0; k + 1 < kPacked + 1 && k < kPacked; k += 2) {
             const f2 ax = {q[k], q[k + 1]}, au = {q[KC + k], q[KC + k + 1]}, lc = {q[2 * KC + k], q[2 * KC + k + 1]};
             const f2 e = __builtin_elementwise_fma(c2, ax, __builtin_elementwise_fma(s2, au, lc));
-            sum += __builtin_amdgcn_exp2f(e.x);
+            sum = k == 0 ? __builtin_amdgcn_exp2f(e.x) : sum + __builtin_amdgcn_exp2f(e.x);
             sum += __builtin_amdgcn_exp2f(e.y);
         }
 #pragma unroll
-        for (int k = kPacked; k < KC; ++k) sum += __builtin_amdgcn_exp2f(fmaf(c, q[k], fmaf(s, q[KC + k], q[2 * KC + k])));
-        const float margin = q[3 * KC];
-        return sum < 1.0f - margin ? -1 : (sum > 1.0f + margin ? 1 : 0);
+        for (int k = kPacked; k < KC; ++k) {
+            const float t = __builtin_amdgcn_exp2f(fmaf(c, q[k], fmaf(s, q[KC + k], q[2 * KC + k])));
+            sum = k == 0 ? t : sum + t;
+        }
+        // One subtraction a try instead of forming 1 - margin and 1 + margin: sum - 1 is exact for sum in [0.5, 2] (Sterbenz), so
+        // there the test is the real-number test sum < 1 - margin / sum > 1 + margin the margin was derived for; outside, the
+        // verdict is certain either way (margin < 0.25, or infinite: every try undecided).  A NaN sum stays undecided.
+        // Not the old test bit for bit: where fl(1 -+ margin) rounded, a sum one float from it may now be called certain (or
+        // undecided) where it was not -- both tests are rigorous, so the chains are the same; the undecided share may move by
+        // that one-float band (tests/test_screen_margin_test.py).
+        const float margin = q[3 * KC], dev = sum - 1.0f;
+        return dev < -margin ? -1 : (dev > margin ? 1 : 0);
     }
     __device__ __forceinline__ double level_exact(const Coef &cf, double c, double s) const
     {
@@ -724,6 +736,32 @@ __host__ __device__ constexpr size_t screen_lds_doubles()
                                                       : 0);
 }
 
+#if defined(GSSS_COUNT_SERVICE)
+// A/B counter build (GSSS_HIPCC_FLAGS=-DGSSS_COUNT_SERVICE, never in the default library): what the service phases of
+// screened_kernel serve, summed over a launch's wavefronts; the launch's last wavefront prints the sums
+// (tools/count_service.py).  [0] service phases  [1] ... with a double-precision decision  [2] decisions  [3] ... accepted
+// [4] lanes finalised  [5] lanes set up  [6] try iterations  [7] phases whose every set-up lane held a certain accept that
+// had sat idle through a try iteration (the only lanes that could have drawn the step's block 0 in that iteration).
+// The last wavefront is found by a ticket against gridDim.x * kBlock / warpSize: it assumes launches of kBlock threads whose
+// every wavefront reaches the end of the kernel -- a launch that breaks off leaves its sums and the ticket to the next one.
+static __device__ unsigned long long gsss_svc_count[8];
+static __device__ unsigned int gsss_svc_ticket;
+__device__ __forceinline__ void svc_count_flush(const unsigned long long (&c)[8])
+{
+    if ((threadIdx.x & (warpSize - 1)) == 0) {
+        for (int i = 0; i < 8; ++i) __hip_atomic_fetch_add(&gsss_svc_count[i], c[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned int waves = gridDim.x * (kBlock / warpSize);
+        if (__hip_atomic_fetch_add(&gsss_svc_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == waves - 1) {
+            unsigned long long s[8];
+            for (int i = 0; i < 8; ++i) s[i] = __hip_atomic_exchange(&gsss_svc_count[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&gsss_svc_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            printf("gsss-svc phases %llu decide_phases %llu decides %llu decide_accepts %llu finalised %llu setups %llu "
+                   "try_iters %llu all_idle_accept_phases %llu\n", s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]);
+        }
+    }
+}
+#endif
+
 __device__ __forceinline__ void lds_trade(float &a, int32_t &b, unsigned long long *slot)
 {
     const unsigned long long mine = (unsigned long long)__float_as_uint(a) | ((unsigned long long)(uint32_t)b << 32);
@@ -975,10 +1013,13 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         }
         // (odd / mid-block: the tries before this one were made already -- the last of them decided in double precision)
         const int first = REPLAY ? 0 : (cur.t & (kPerAttempt - 1));
+        // Try h runs when the tries first .. h - 1 ran (t = t0 + h - first) and it is the first or t < max_tries: as t0 < max_tries,
+        // that is h < lim -- one comparison a try instead of two
+        const int lim = first + (max_tries - cur.t);
         bool stopped = false;
 #pragma unroll
         for (int h = 0; h < kPerAttempt; ++h) {
-            if (!stopped && h >= first && (h == first || cur.t < max_tries) &&
+            if (!stopped && h >= first && h < lim &&
                 !(REPLAY && (cur.err & GSSS_CHAIN_REPLAY_EXHAUSTED))) {
                 double uu;
                 if constexpr (kTry32)
@@ -1207,6 +1248,10 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     if (cur.status == kPending) setup();
 
     bool stuck = false;
+#if defined(GSSS_COUNT_SERVICE)
+    unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool idle_accept = false;  // the current chain is a certain accept that sat out a try iteration
+#endif
     for (;;) {
         // a lane whose current chain cannot try (stopped, waiting or finished) takes its other chain when that one can
         if (TP::kTradeMin > 1) {
@@ -1216,6 +1261,10 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         } else if (kPark && cur.status != kReady && parked_status == kReady)
             trade();
         const unsigned long long trying = __ballot(cur.status == kReady);
+#if defined(GSSS_COUNT_SERVICE)
+        cnt[6] += trying != 0ull;
+        if (cur.status == kFinalAccept || cur.status == kFinalAccept + kFinalInHi) idle_accept = true;
+#endif
         if (cur.status == kReady) attempt();
         const unsigned long long live = __ballot(cur.status != kDone || parked_status != kDone);
         if (live == 0ull) break;
@@ -1228,8 +1277,28 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         const bool service = pend != 0ull && (kSvcWaitDen * __popcll(waiting) >= kSvcWaitNum * n_live ||
                                               kSvcPendDen * __popcll(pend) >= kSvcPendNum * n_live);
         if (service) {
+#if defined(GSSS_COUNT_SERVICE)
+            const bool was_idle = idle_accept && needs_service(cur.status);
+#endif
             if (kPark && !needs_service(cur.status) && needs_service(parked_status)) trade();  // bring the waiting chain in
+#if defined(GSSS_COUNT_SERVICE)
+            if (!was_idle) idle_accept = false;
+            const bool dec = is_decide(cur.status);
+            const unsigned long long fin = __ballot(is_final(cur.status)), decs = __ballot(dec);
+#endif
             if (is_final(cur.status)) finalise();
+#if defined(GSSS_COUNT_SERVICE)
+            const unsigned long long dec_acc = __ballot(dec && cur.status != kReady);
+            const unsigned long long sets = __ballot(cur.status == kPending), idle_sets = __ballot(cur.status == kPending && idle_accept);
+            cnt[0] += 1;
+            cnt[1] += decs != 0ull;
+            cnt[2] += __popcll(decs);
+            cnt[3] += __popcll(dec_acc);
+            cnt[4] += __popcll(fin);
+            cnt[5] += __popcll(sets);
+            cnt[7] += sets != 0ull && sets == idle_sets;
+            idle_accept = false;
+#endif
             if (cur.status == kPending) setup();
         }
         if (trying == 0ull && !service && __ballot(kPark && cur.status != kReady && parked_status == kReady) == 0ull) {
@@ -1248,6 +1317,9 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         flush();
     }
     if (sliced) SliceSched::publish<kThrough>(a, sched_word);
+#if defined(GSSS_COUNT_SERVICE)
+    svc_count_flush(cnt);
+#endif
 }
 
 // numpy's stream through the screened kernel: one lane per chain, unsliced (a generator's state lives in its lane for the launch)
