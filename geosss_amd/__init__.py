@@ -9,7 +9,7 @@ Drop-in for the slice-sampler path of microscopic-image-analysis/geosss:
 from . import _lib, diagnostics, io, pointcloud, rand, registration, sphere, spherical_curve
 from .diagnostics import IAT, acf, acf_fft, distance, n_eff
 from .distributions import (ACG, Bingham, BinghamFisher, CurvedVonMisesFisher, Distribution, MarginalVonMisesFisher, MixtureModel,
-                            MultivariateNormal, SlerpCurve, Uniform, VonMisesFisher, brownian_curve, constrained_brownian_curve, distance_slerp,
+                            MultivariateNormal, SlerpCurve, TargetBatch, Uniform, VonMisesFisher, brownian_curve, constrained_brownian_curve, distance_slerp,
                             random_bingham)
 from .mcmc import (IndependenceSampler, MetropolisHastings, MixtureRWMHIndependenceSampler, RejectionSphericalSliceSampler,
                    ShrinkageSphericalSliceSampler, SphericalHMC, determine_burnin)
@@ -20,7 +20,7 @@ from .sphere import (cartesian2polar, cartesian2spherical, givens, orthogonal_pr
 from .usertarget import DeviceDistribution
 from .utils import SamplerLauncher, colors, count_calls, counter, take_time
 
-__all__ = ["Bingham", "BinghamFisher", "CurvedVonMisesFisher", "DeviceDistribution", "Distribution", "MixtureModel", "SlerpCurve", "VonMisesFisher",
+__all__ = ["Bingham", "BinghamFisher", "CurvedVonMisesFisher", "DeviceDistribution", "Distribution", "MixtureModel", "SlerpCurve", "TargetBatch", "VonMisesFisher",
            "brownian_curve", "random_bingham", "RejectionSphericalSliceSampler", "ShrinkageSphericalSliceSampler",
            "MetropolisHastings", "SphericalHMC", "IndependenceSampler", "MixtureRWMHIndependenceSampler", "determine_burnin", "sample_sphere", "sample_sphere_device", "SamplerLauncher", "count_calls", "counter", "take_time",
            "sphere", "diagnostics", "registration", "rand", "sample_vMF", "sample_bingham", "sample_bingham_2d", "sample_bingham_3d", "CoherentPointDrift", "GaussianMixtureModel", "PointCloud", "RotationProjection", "IAT", "acf", "acf_fft", "distance", "n_eff",

@@ -52,6 +52,7 @@ SIGNATURES = {
     "gsss_device_count": (C.c_int, []),
     "gsss_target_create": (C.c_int, [C.POINTER(TargetDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "gsss_target_create_mixture": (C.c_int, [C.POINTER(TargetDesc), C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "gsss_target_create_batch": (C.c_int, [C.POINTER(TargetDesc), C.c_int32, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gsss_exact_layout": (C.c_int, [C.c_int32]),
     "gsss_target_create_user": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "gsss_target_destroy": (C.c_int, [C.c_void_p]),

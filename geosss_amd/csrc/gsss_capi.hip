@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "gsss_batch.h"
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
@@ -398,7 +399,17 @@ struct gsss_target {
     size_t blob_doubles;
     int cpd_variant;  // GSSS_CPD: which registration kernel (neighbour-list size, uniform source weights)
     const UserModuleTable *user;  // GSSS_USER: the compiled module's launchers (gsss_user_target.h)
+    BatchInfo batch;  // gsss_target_create_batch: n_targets > 0 -- blob_dev holds every member's blob, tb describes any one of them
 };
+
+static bool is_batch(const gsss_target *t) { return t->batch.n_targets > 0; }
+
+static int batch_fast_dispatch(const gsss::TargetBlock &tb, const gsss::RunBlock &rb, const gsss::BatchInfo &bi, gsss::FastProbe *probe,
+                               hipStream_t st)
+{
+    if (tb.kind == GSSS_VMF_MIXTURE) return gsss::launch_batch_fast_vmf(tb, rb, bi, probe, st);
+    return gsss::launch_batch_fast_bingham(tb, rb, bi, probe, st);
+}
 
 // The parameter blob of one target (layout per kind: TargetBlock::blob); gsss_target_create, and per component
 // gsss_target_create_mixture
@@ -702,6 +713,115 @@ int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_com
     return GSSS_OK;
 }
 
+int gsss_target_create_batch(const gsss_target_desc *targets, int32_t n_targets, int64_t chains_per_target, int device,
+                             gsss_target **out)
+{
+    if (!targets || !out) {
+        set_error("null argument");
+        return GSSS_E_INVALID;
+    }
+    *out = nullptr;
+    if (n_targets < 1 || chains_per_target < 1) {
+        set_error("a target batch needs at least one target and one chain per target (got %d, %lld)", n_targets,
+                  (long long)chains_per_target);
+        return GSSS_E_INVALID;
+    }
+    if (chains_per_target > 0x7FFFFFFFll - 1024) {
+        set_error("a target batch takes at most 2^31-1025 chains per target");
+        return GSSS_E_UNSUPPORTED;
+    }
+    const int kind = targets[0].kind, d = targets[0].d, k = targets[0].k;
+    if (kind != GSSS_VMF_MIXTURE && kind != GSSS_BINGHAM) {
+        set_error("a target batch holds vMF mixtures (GSSS_VMF_MIXTURE) or Bingham / Fisher-Bingham targets (GSSS_BINGHAM): kind %d "
+                  "(curve-vMF, registration, GSSS_MIXTURE and user targets) is not built as a batch member", kind);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (d < 2) {
+        set_error("d must be >= 2 (got %d)", d);
+        return GSSS_E_INVALID;
+    }
+    if (select_vec(d, 0) < 0) return GSSS_E_UNSUPPORTED;
+    // every member as gsss_target_create packs it, at an equal stride (the blob's size follows from kind, d and K)
+    std::vector<double> all;
+    size_t stride = 0;
+    bool all_diagonal = true;
+    double scale_all = 0.0;
+    for (int t = 0; t < n_targets; ++t) {
+        const gsss_target_desc *desc = targets + t;
+        if (desc->kind != kind) {
+            set_error("the members of a target batch are of one family (member 0 has kind %d, member %d kind %d)", kind, t, desc->kind);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (desc->d != d) {
+            set_error("the members of a target batch share d (member 0 has d=%d, member %d d=%d)", d, t, desc->d);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (kind == GSSS_VMF_MIXTURE && desc->k != k) {
+            set_error("the vMF mixtures of a target batch share K (member 0 has K=%d, member %d K=%d)", k, t, desc->k);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (kind == GSSS_BINGHAM && (desc->mu != nullptr) != (targets[0].mu != nullptr)) {
+            set_error("the Bingham members of a target batch all have a linear term b or none has (member 0 %s, member %d %s)",
+                      targets[0].mu ? "has one" : "has none", t, desc->mu ? "has one" : "has none");
+            return GSSS_E_UNSUPPORTED;
+        }
+        std::vector<double> part;
+        bool diagonal = false;
+        double scale = 0.0;
+        int cpd_variant = 0;
+        if (int rc = pack_target(desc, part, diagonal, scale, cpd_variant)) {
+            std::string msg = g_err;
+            set_error("member %d: %s", t, msg.c_str());
+            return rc;
+        }
+        if (t == 0) {
+            stride = part.size();
+            all.reserve(stride * (size_t)n_targets);
+        }
+        if (part.size() != stride) {
+            set_error("corrupt target batch: member %d packs to another size", t);
+            return GSSS_E_INVALID;
+        }
+        all.insert(all.end(), part.begin(), part.end());
+        all_diagonal = all_diagonal && diagonal;
+        scale_all = std::fmax(scale_all, scale);
+    }
+    int ndev = gsss_device_count();
+    if (ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("device %d not available (%d HIP devices visible)", device, ndev);
+        return GSSS_E_NO_DEVICE;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    gsss_target *t = new (std::nothrow) gsss_target();
+    if (!t) {
+        set_error("out of host memory");
+        return GSSS_E_INVALID;
+    }
+    t->device = device;
+    t->blob_doubles = all.size();
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), all.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(t->blob_dev, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error("copying target parameters failed: %s", hipGetErrorString(e));
+        if (t->blob_dev) (void)hipFree(t->blob_dev);
+        delete t;
+        return GSSS_E_HIP;
+    }
+    t->tb.blob = t->blob_dev;
+    t->tb.kind = kind;
+    t->tb.d = d;
+    // Bingham: the flags of gsss_target_create -- the diagonal kernels only if EVERY member's A is diagonal
+    t->tb.k = kind == GSSS_BINGHAM ? ((all_diagonal ? 1 : 0) | (targets[0].mu ? 2 : 0)) : k;
+    t->tb.dpad = 0;
+    t->tb.kappa = 0.0;
+    t->tb.scale = scale_all;
+    t->cpd_variant = 0;
+    t->batch = BatchInfo{n_targets, (int64_t)stride, chains_per_target};
+    *out = t;
+    return GSSS_OK;
+}
+
 int gsss_exact_layout(int32_t d)
 {
     if (d < 2) {
@@ -796,6 +916,10 @@ static int logprob_or_gradient(const gsss_target *t, const double *x_dev, int64_
         set_error(grad ? "bad argument to gsss_gradient" : "bad argument to gsss_logprob");
         return GSSS_E_INVALID;
     }
+    if (is_batch(t)) {
+        set_error("%s is not built for a target batch: evaluate the members' own handles", grad ? "gsss_gradient" : "gsss_logprob");
+        return GSSS_E_UNSUPPORTED;
+    }
     if (n == 0) return GSSS_OK;
     const int vec = select_vec_for(t->tb, 0);
     if (vec < 0) return vec;
@@ -861,6 +985,38 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
     if (a->chain_offset + (uint64_t)a->n_chains > (1ull << 48) || a->step_offset + (uint64_t)a->n_steps >= kInitStep) {
         set_error("chain / step ids exceed the 48-bit counter space");
         return GSSS_E_INVALID;
+    }
+    if (is_batch(t)) {  // (before anything runs: a refused launch of a batch leaves every buffer as it was)
+        const int64_t m = t->batch.m;
+        if (mh) {
+            set_error("a target batch is sampled by GSSS_SHRINK and GSSS_REJECT only: the Metropolis-Hastings / HMC kernels (sampler %d) "
+                      "have no batch build", a->sampler);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (a->replay_dev || a->rng_state_dev) {
+            set_error("a target batch runs on the library (Philox) stream only: no %s", a->replay_dev ? "replay_dev" : "rng_state_dev");
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (a->stats_dev) {
+            set_error("running statistics (stats_dev) take one set of directions: they are not built for a target batch");
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (a->chain_offset % (uint64_t)m != 0) {
+            set_error("target batch: chain_offset %llu is not a multiple of the %lld chains per target (a launch starts at a target's "
+                      "first chain)", (unsigned long long)a->chain_offset, (long long)m);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (a->n_chains % m != 0) {
+            set_error("target batch: n_chains %lld is not a multiple of the %lld chains per target (a launch ends at a target's last "
+                      "chain)", (long long)a->n_chains, (long long)m);
+            return GSSS_E_UNSUPPORTED;
+        }
+        if (a->chain_offset / (uint64_t)m + (uint64_t)(a->n_chains / m) > (uint64_t)t->batch.n_targets) {
+            set_error("target batch: chains %llu .. %llu belong to targets up to %llu, the batch holds %d",
+                      (unsigned long long)a->chain_offset, (unsigned long long)(a->chain_offset + (uint64_t)a->n_chains),
+                      (unsigned long long)(a->chain_offset / (uint64_t)m + (uint64_t)(a->n_chains / m)), t->batch.n_targets);
+            return GSSS_E_UNSUPPORTED;
+        }
     }
     last_launch() = LaunchInfo{0, 0, 0.0};
     if (a->n_chains == 0) return GSSS_OK;
@@ -945,6 +1101,19 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
         return GSSS_E_INVALID;
     }
 
+    if (is_batch(t)) {  // chain c of the launch belongs to target (chain_offset + c) / m: the launch's first target leads the blobs
+        TargetBlock tbb = t->tb;
+        tbb.blob += (int64_t)(a->chain_offset / (uint64_t)t->batch.m) * t->batch.stride;
+        if (a->mode == GSSS_MODE_FAST) {
+            if (a->n_steps > 0x7FFFFFFFll || a->thin > 0x7FFFFFFFll || a->n_chains > 0x7FFFFFFFll - 1024) {
+                set_error("fast mode takes at most 2^31-1 steps / chains per call");
+                return GSSS_E_INVALID;
+            }
+            return batch_fast_dispatch(tbb, rb, t->batch, nullptr, st);
+        }
+        return tbb.kind == GSSS_VMF_MIXTURE ? launch_batch_run_vmf(vec, tbb, rb, t->batch, st)
+                                            : launch_batch_run_bingham(vec, tbb, rb, t->batch, st);
+    }
     const int draws = replay ? kDrawsReplay : (a->rng_state_dev ? kDrawsNumpy : kDrawsPhilox);
     if (a->mode == GSSS_MODE_FAST && a->rng_state_dev) {  // a generator per chain: the lane-per-chain shapes only
         FastProbe pr;
@@ -1035,6 +1204,11 @@ int gsss_mode_supported(const gsss_target *t, int32_t mode)
     if (mode == GSSS_MODE_EXACT) return select_vec(t->tb.d, 0) >= 0;
     if (mode == GSSS_MODE_FAST) {
         FastProbe pr;
+        if (is_batch(t)) {  // (every shape with a batch fast kernel has the screened and the all-double one)
+            RunBlock rbp{};
+            rbp.screen = 1;
+            return batch_fast_dispatch(t->tb, rbp, t->batch, &pr, nullptr) == GSSS_OK;
+        }
         return fast_dispatch(t->tb, RunBlock{}, false, &pr, nullptr) == GSSS_OK;
     }
     return 0;
@@ -1045,6 +1219,11 @@ const char *gsss_variant_name(const gsss_target *t, int32_t mode, int32_t varian
     if (!t) return "";
     if (mode == GSSS_MODE_FAST) {
         FastProbe pr;
+        if (is_batch(t)) {
+            RunBlock rbp{};
+            rbp.screen = 1;
+            return batch_fast_dispatch(t->tb, rbp, t->batch, &pr, nullptr) == GSSS_OK ? "fast-lane" : "";
+        }
         if (fast_dispatch(t->tb, RunBlock{}, false, &pr, nullptr) != GSSS_OK) return "";
         return pr.lane ? "fast-lane" : "fast-coop";
     }
@@ -1066,6 +1245,11 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
     if (mode == GSSS_MODE_FAST) {
         FastProbe pr;
         RunBlock rbp{};
+        if (is_batch(t)) {  // one lane per chain whatever the placement
+            rbp.screen = variant == GSSS_VARIANT_FAST_DOUBLE ? 0 : 1;
+            if (batch_fast_dispatch(t->tb, rbp, t->batch, &pr, nullptr) == GSSS_OK) snprintf(name, sizeof(name), "%s", pr.name);
+            return name;
+        }
         rbp.screen = variant == GSSS_VARIANT_FAST_DOUBLE || spread ? 0 : 1;
         if (fast_dispatch(t->tb, rbp, false, &pr, nullptr) != GSSS_OK) return name;
         if (pr.lane && spread && t->tb.d <= 16)
@@ -1080,7 +1264,7 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
                       : t->tb.kind == GSSS_MIXTURE   ? "Mixture"
                       : t->tb.kind == GSSS_USER      ? "UserTarget"
                                                      : "CurveVmf";
-    if (vec[0]) snprintf(name, sizeof(name), "run_kernel<%s, %s>", vec, tgt);
+    if (vec[0]) snprintf(name, sizeof(name), "run_kernel<%s, %s%s>", vec, tgt, is_batch(t) ? ", batch" : "");
     return name;
 }
 

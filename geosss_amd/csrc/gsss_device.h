@@ -69,6 +69,22 @@ struct RunBlock {
                                // (the lane kernels slice only the last, partial round of their workgroups)
 };
 
+// A batch of targets in one launch (gsss_target_create_batch: M members of one family and shape, their blobs at an equal stride;
+// target t owns the chains [t m, (t + 1) m) of the launch).  The batch builds of the sampler kernels (their last template flag,
+// BATCH) take it as a further by-value argument; their grid is targets x chunks, and workgroup b serves chunk b % chunks of
+// target b / chunks: it stages blob + (b / chunks) stride and maps its lanes to the chains t m + ..., bounded by (t + 1) m.
+// All of it is used before the first step only.  The builds without the flag take no such argument and compile as they did.
+struct BatchBlock {
+    int64_t stride;  // doubles from one member's blob to the next
+    int32_t m;       // chains per target
+    int32_t chunks;  // workgroups per target: ceil(m / chains per workgroup)
+};
+template <class T>
+__device__ __forceinline__ const T &first_of(const T &x)
+{
+    return x;
+}
+
 // ------------------------------------------------------------------------------------------
 // Slice scheduler.  The workgroup that draws ticket t works on (slice t / n_chunks, chunk t % n_chunks); slice k of a chunk
 // starts when slice k - 1 has been published.  Tickets, not blockIdx: the predecessor's ticket was drawn earlier, so its
@@ -1746,13 +1762,17 @@ __host__ __device__ constexpr size_t scratch_doubles()
     return (size_t)T::kScratchPerChain * (kBlock / V::L);
 }
 
-template <class V, template <class> class TT, template <class> class DR, bool STATS = false>
-__global__ void __launch_bounds__(kBlock) run_kernel(TargetBlock tb, RunBlock a)
+// BATCH (last flag; BB = BatchBlock, a further by-value argument): the batch build -- this workgroup's target and chunk of that
+// target's chains follow from blockIdx.x (BatchBlock above); library stream, no running statistics.
+template <class V, template <class> class TT, template <class> class DR, bool STATS = false, bool BATCH = false, class... BB>
+__global__ void __launch_bounds__(kBlock) run_kernel(TargetBlock tb, RunBlock a, BB... batch)
 {
+    static_assert(sizeof...(BB) == (BATCH ? 1 : 0) && !(BATCH && STATS), "the batch build takes one BatchBlock and keeps no statistics");
     using T = TT<V>;
     using Draws = DR<V>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     T tgt;
+    if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
     tgt.stage(lds, tb);
     double *scratch = lds + T::lds_doubles(tb.k, tb.d) + (size_t)T::kScratchPerChain * (threadIdx.x / V::L);
     Draws dr;
@@ -1765,10 +1785,18 @@ __global__ void __launch_bounds__(kBlock) run_kernel(TargetBlock tb, RunBlock a)
     // packed: consecutive lane groups take consecutive chains.  spread (lane layouts, small ensembles):
     // one chain per wavefront -- lane 0 owns it, the other lanes shadow it, so the wave never diverges
     const bool spread = V::L == 1 && a.spread;
-    const int64_t c_raw = spread ? (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64
-                                 : (int64_t)blockIdx.x * (kBlock / V::L) + threadIdx.x / V::L;
-    const bool active = c_raw < n && (!spread || threadIdx.x % 64 == 0);
-    const int64_t c = c_raw < n ? c_raw : n - 1;  // surplus lanes shadow a chain and store nothing
+    int64_t c_raw = spread ? (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64
+                           : (int64_t)blockIdx.x * (kBlock / V::L) + threadIdx.x / V::L;
+    bool active = c_raw < n && (!spread || threadIdx.x % 64 == 0);
+    int64_t c = c_raw < n ? c_raw : n - 1;  // surplus lanes shadow a chain and store nothing
+    if constexpr (BATCH) {  // chunk bl of target bt: the same rule within the target's block of chains [bt m, c_end)
+        const BatchBlock &bb = first_of(batch...);
+        const int64_t bt = (int64_t)(blockIdx.x / (uint32_t)bb.chunks), bl = (int64_t)blockIdx.x - bt * bb.chunks;
+        const int64_t c_end = (bt + 1) * bb.m < n ? (bt + 1) * bb.m : n;
+        c_raw = bt * bb.m + (spread ? bl * (kBlock / 64) + threadIdx.x / 64 : bl * (kBlock / V::L) + threadIdx.x / V::L);
+        active = c_raw < c_end && (!spread || threadIdx.x % 64 == 0);
+        c = c_raw < c_end ? c_raw : c_end - 1;
+    }
 
     double x[V::N];
 #pragma unroll

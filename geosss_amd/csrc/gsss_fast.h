@@ -556,14 +556,19 @@ __host__ __device__ constexpr size_t fast_lds_doubles()
 // NUMPY: the draws come from numpy's own PCG64 / ziggurat stream (rng_state, NumpyDraws) instead of the replay buffer, at
 // the replay path's consumption points -- the reference's own order, a uniform per try that is made and none for one that is
 // not.  A generator per chain: one chain per lane (nothing is parked), the ziggurat tables where the parked chains would be.
-template <int D, class TP, bool REPLAY, bool STATS = false, bool NUMPY = false>
-__global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a)
+// BATCH (last flag, default false; BB = BatchBlock, a further by-value argument, gsss_device.h): the batch build -- workgroup b
+// serves chunk b % chunks of target b / chunks, one chain per lane, nothing parked (launched packed).
+template <int D, class TP, bool REPLAY, bool STATS = false, bool NUMPY = false, bool BATCH = false, class... BB>
+__global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a, BB... batch)
 {
     static_assert(!NUMPY || REPLAY, "numpy's stream is a sequential source: it is read where the replay buffer is");
+    static_assert(sizeof...(BB) == (BATCH ? 1 : 0) && !(BATCH && (REPLAY || STATS || NUMPY)),
+                  "the batch build takes one BatchBlock: library stream, no running statistics");
     using V = LaneVec<D>;
     using Chain = FastChain<D, TP>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     TP tp;
+    if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
     tp.stage(lds, tb);
     const fm::Tables tab = stage_tables(lds + TP::lds_doubles());
     // word w of this lane's parked chain lives at park[w * kBlock]: conflict-free across lanes
@@ -578,14 +583,20 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
     const int32_t thin = (int32_t)a.thin;
     const int32_t max_tries = a.max_tries < (1 << 26) ? a.max_tries : (1 << 26) - 1;  // t shares a word with the flags
     constexpr uint32_t kTryBase = 1u + (uint32_t)((D + 3) / 4);
-    constexpr bool kPark = fast_parks<D, TP>() && !NUMPY;
+    constexpr bool kPark = fast_parks<D, TP>() && !NUMPY && !BATCH;
     constexpr int kPerBlock = kPark ? 2 * kBlock : kBlock;
     // packed: lane l of block b owns chains b*P + l and (parking targets) b*P + 256 + l.
     // spread (small ensembles): one chain per wavefront, owned by its lane 0; nothing is parked.
     const bool spread = a.spread != 0;
-    const int32_t id0 = spread ? ((threadIdx.x % 64 == 0) ? (int32_t)blockIdx.x * (kBlock / 64) + (int32_t)threadIdx.x / 64 : n)
-                               : (int32_t)blockIdx.x * kPerBlock + (int32_t)threadIdx.x;
-    const int32_t id1 = spread ? n : id0 + kBlock;
+    int32_t id0 = spread ? ((threadIdx.x % 64 == 0) ? (int32_t)blockIdx.x * (kBlock / 64) + (int32_t)threadIdx.x / 64 : n)
+                         : (int32_t)blockIdx.x * kPerBlock + (int32_t)threadIdx.x;
+    if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
+        const BatchBlock &bb = first_of(batch...);
+        const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
+        const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;
+        id0 = (id < ((int64_t)t + 1) * bb.m && id < (int64_t)n) ? (int32_t)id : n;
+    }
+    const int32_t id1 = (BATCH || spread) ? n : id0 + kBlock;
 
     Chain cur;
     int32_t slot = 0;               // which of the lane's two chains `cur` is

@@ -802,15 +802,22 @@ __device__ __forceinline__ void lds_trade(float &a, float &b, unsigned long long
 // is made -- a generator per chain, one chain per lane, the ziggurat tables where second chains would be parked.  The tries are
 // screened like the library stream's: the same accept decisions as fast_kernel<.., NUMPY>, hence the reference's chain from its
 // seed (tests/test_hip_parity.py::test_reference_chain_from_seed[packed], test_numpy_stream_lane_kernel).
-template <int D, class TP, bool REPLAY, bool STATS = false, bool STAGE = false, bool NUMPY = false>
+// BATCH (last flag, default false; BB = BatchBlock, a further by-value argument, gsss_device.h): the batch build -- workgroup b
+// serves chunk b % chunks of target b / chunks: it stages that member's blob and gives its lanes that target's chains, one chain
+// per lane (launched with one_per_lane and without a slice plan), no code for a parked chain.  All of it happens before the first
+// step: a lane past its target's block takes the chain id n, as the empty second slot of a one-per-lane launch does.
+template <int D, class TP, bool REPLAY, bool STATS = false, bool STAGE = false, bool NUMPY = false, bool BATCH = false, class... BB>
 __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (NUMPY ? TP::kNumpyWaves : TP::kMinWaves))
-    screened_kernel(TargetBlock tb, RunBlock a)  // (NUMPY: the generator's state and the ziggurat's temporaries on top of the plain kernel's registers)
+    screened_kernel(TargetBlock tb, RunBlock a, BB... batch)  // (NUMPY: the generator's state and the ziggurat's temporaries on top of the plain kernel's registers)
 {
     static_assert(!NUMPY || (REPLAY && !STAGE), "numpy's stream is a sequential source: it is read where the replay buffer is");
+    static_assert(sizeof...(BB) == (BATCH ? 1 : 0) && !(BATCH && (REPLAY || STATS || STAGE || NUMPY)),
+                  "the batch build takes one BatchBlock: library stream, no running statistics");
     using V = LaneVec<D>;
     using Chain = ScreenChain<D, TP>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     TP tp;
+    if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
     tp.stage(lds, tb);
     const fm::Tables tab = stage_tables(lds + TP::lds_doubles());
     unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + TP::lds_doubles() + kTabLds) + threadIdx.x;
@@ -832,7 +839,7 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     // This workgroup's work: its chunk of chains for the whole launch -- or, in the sliced partial round of a launch
     // (plan_partial_round, gsss_device.h), the (chunk, step slice) of the ticket it draws.  A chain's step count runs over the
     // launch's steps [s_begin, n_steps): counters of the stream and retained rows need nothing else.
-    constexpr int kChunk = (screen_parks<D, TP>() && !NUMPY && !STAGE) ? 2 * kBlock : kBlock;  // chains per workgroup
+    constexpr int kChunk = (screen_parks<D, TP>() && !NUMPY && !STAGE && !BATCH) ? 2 * kBlock : kBlock;  // chains per workgroup
     __shared__ uint32_t sched_word[4];
     const bool sliced = a.sched != nullptr && (int32_t)blockIdx.x >= a.sched_first;
     uint32_t chunk = blockIdx.x;
@@ -848,10 +855,16 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     const double rcp_thin = 1.0 / (double)thin;  // (compact chains: the retained row follows from the step count)
     const int32_t max_tries = a.max_tries < (1 << 25) ? a.max_tries : (1 << 25) - 1;  // t shares a word with the flags
     constexpr uint32_t kTryBase = 1u + (uint32_t)((D + 3) / 4);
-    constexpr bool kPark = screen_parks<D, TP>() && !NUMPY && !STAGE;  // (NUMPY: a generator per chain; STAGE: built for one chain per lane)
+    constexpr bool kPark = screen_parks<D, TP>() && !NUMPY && !STAGE && !BATCH;  // (NUMPY: a generator per chain; STAGE, BATCH: built for one chain per lane)
     constexpr int kPerBlock = kPark ? 2 * kBlock : kBlock;
     // (one_per_lane: kBlock chains per workgroup, the lane's second slot stays empty -- a chain id past the ensemble)
-    const int32_t id0 = (int32_t)chunk * (a.one_per_lane ? kBlock : kPerBlock) + (int32_t)threadIdx.x;
+    int32_t id0 = (int32_t)chunk * (a.one_per_lane ? kBlock : kPerBlock) + (int32_t)threadIdx.x;
+    if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
+        const BatchBlock &bb = first_of(batch...);
+        const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
+        const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;
+        id0 = (id < ((int64_t)t + 1) * bb.m && id < (int64_t)n) ? (int32_t)id : n;
+    }
     const int32_t id1 = a.one_per_lane ? n : id0 + kBlock;
 
     Chain cur;

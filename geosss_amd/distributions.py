@@ -26,7 +26,7 @@ from . import _lib
 from .sphere import _device_index, current_stream_ptr
 
 __all__ = ["Distribution", "VonMisesFisher", "MixtureModel", "Bingham", "BinghamFisher", "CurvedVonMisesFisher", "SlerpCurve",
-           "random_bingham", "brownian_curve", "counted"]
+           "TargetBatch", "random_bingham", "brownian_curve", "counted"]
 
 
 def counted(fn):
@@ -83,6 +83,17 @@ class _DeviceTarget:
             h = C.c_void_p()
             _lib.check(self.lib.gsss_target_create_mixture(descs, len(comps), logw.ctypes.data_as(C.c_void_p), device,
                                                            C.byref(h)))
+            self.handle = h
+            return
+        if extra is not None and "batch" in extra:  # extra: the members' packs and the chains per target (TargetBatch._pack)
+            members = extra["batch"]
+            descs = (_lib.TargetDesc * len(members))()
+            for i, (mkind, md, mk, mkappa, arrays) in enumerate(members):
+                descs[i] = _lib.TargetDesc(mkind, md, mk, 0,
+                                           *[a.ctypes.data_as(C.c_void_p) if a is not None else None for a in arrays],
+                                           float(mkappa))
+            h = C.c_void_p()
+            _lib.check(self.lib.gsss_target_create_batch(descs, len(members), int(extra["chains_per_target"]), device, C.byref(h)))
             self.handle = h
             return
         if kind == _lib.USER:  # extra: the compiled module's table (usertarget.DeviceDistribution._pack)
@@ -411,6 +422,117 @@ class MixtureModel(Distribution):
         if self._marginal:
             return _HostDensity._pack(self)
         return self._gradient_device(x)
+
+
+class TargetBatch(Distribution):
+    """M targets of one family and one shape, sampled in ONE launch: target t owns the contiguous block of chains
+    [t m, (t + 1) m) in global chain ids, m = chains per target (the sampler derives it as n_chains / M; initial states are
+    target-major).  The chains are those of M separate samplers, each on member t alone with the same seed and
+    chain_offset = t m, bit for bit.
+
+    Members: all `VonMisesFisher` / `MixtureModel` of vMF terms with the same number of terms K, or all `Bingham` /
+    `BinghamFisher` (all with or all without b; `Uniform(d)` is a Bingham with A = 0), of one dimension.  A batch whose members
+    are all diagonal-A Bingham runs the diagonal fast kernels, a batch that mixes diagonal and dense A the dense ones.
+    Samplers: the two slice samplers on the library (Philox) stream; the Metropolis-Hastings / HMC classes, rng='numpy',
+    replay and running statistics are refused.  `log_prob` / `gradient` take (M, n, d) and return (M, n) / (M, n, d), member
+    by member.  Editing a member's parameters re-uploads the batch, as for MixtureModel."""
+
+    def __init__(self, pdfs):
+        self.pdfs = list(pdfs)
+        if not self.pdfs:
+            raise TypeError("a target batch needs at least one member")
+        packs = self._member_packs()
+        kind, d, k = packs[0][:3]
+        for i, (mk, md, mkk, _, arrays) in enumerate(packs):
+            if mk != kind:
+                raise TypeError(f"the members of a target batch are of one family: member 0 is a {self._family(kind)}, "
+                                f"member {i} a {self._family(mk)}")
+            if md != d:
+                raise ValueError(f"the members of a target batch share the dimension: member 0 has d={d}, member {i} d={md}")
+            if kind == _lib.VMF_MIXTURE and mkk != k:
+                raise ValueError(f"the vMF mixtures of a target batch share the number of terms: member 0 has K={k}, "
+                                 f"member {i} K={mkk}")
+            if kind == _lib.BINGHAM and (arrays[0] is None) != (packs[0][4][0] is None):
+                raise ValueError("the Bingham members of a target batch all have a linear term b (BinghamFisher) or none has: "
+                                 f"member 0 and member {i} differ")
+
+    @staticmethod
+    def _family(kind):
+        return {_lib.VMF_MIXTURE: "vMF mixture", _lib.BINGHAM: "Bingham target"}.get(kind, f"target of kind {kind}")
+
+    def _member_packs(self):
+        packs = []
+        for i, p in enumerate(self.pdfs):
+            if isinstance(p, TargetBatch):
+                raise TypeError(f"member {i}: a TargetBatch is not a member of a target batch (concatenate the members instead)")
+            if getattr(p, "_device_source", False):
+                raise TypeError(f"member {i}: a DeviceDistribution (user target) is not built as a batch member")
+            if not isinstance(p, Distribution):
+                raise TypeError(f"member {i}: {type(p).__name__} is not a device target")
+            if isinstance(p, _HostDensity) or (isinstance(p, MixtureModel) and p._marginal):
+                raise TypeError(f"member {i}: {type(p).__name__} is a host-side density, not a device target")
+            if not isinstance(p, (VonMisesFisher, MixtureModel, Bingham)):
+                raise TypeError(f"member {i}: {type(p).__name__} is not built as a batch member: members are VonMisesFisher, "
+                                "MixtureModel of vMF terms, Bingham and BinghamFisher")
+            pack = p._pack()
+            if pack[0] not in (_lib.VMF_MIXTURE, _lib.BINGHAM):
+                raise TypeError(f"member {i}: a MixtureModel with other than vMF terms (GSSS_MIXTURE) is not built as a batch "
+                                "member: members are VonMisesFisher, MixtureModel of vMF terms, Bingham and BinghamFisher")
+            packs.append(tuple(pack[:5]))
+        return packs
+
+    def __len__(self):
+        return len(self.pdfs)
+
+    @property
+    def d(self):
+        return self.pdfs[0].d
+
+    def _pack(self, chains_per_target=1):
+        """The first member's (kind, d, k, kappa) -- the shape every member has -- and the members' own packs, in order."""
+        packs = self._member_packs()
+        kind, d, k, kappa = packs[0][:4]
+        return kind, d, k, kappa, (), {"batch": packs, "chains_per_target": int(chains_per_target)}
+
+    @staticmethod
+    def _device_key(packed):
+        kind, d, k, kappa = packed[:4]
+        extra = packed[5]  # every member's parameter bytes: editing pdfs[t].A re-uploads
+        return (("batch", kind, d, k, kappa, extra["chains_per_target"]) +
+                tuple((m[:4],) + tuple(a.tobytes() if a is not None else None for a in m[4]) for m in extra["batch"]))
+
+    def _device_target(self, device=None, chains_per_target=1):
+        """The handle carries the chains per target (gsss_target_create_batch): one device copy per (device, m)."""
+        dev = _device_index(device)
+        packed = self._pack(chains_per_target)
+        kind, d, k, kappa, arrays, extra = packed
+        key = self._device_key(packed)
+        cache = self.__dict__.setdefault("_targets", {})
+        hit = cache.get((dev, int(chains_per_target)))
+        if hit is None or hit[0] != key:
+            cache[(dev, int(chains_per_target))] = (key, _DeviceTarget(arrays, kind, d, k, kappa, dev, extra))
+        return cache[(dev, int(chains_per_target))][1]
+
+    def _per_member(self, x, what):
+        M, d = len(self.pdfs), self.d
+        if isinstance(x, torch.Tensor):
+            if x.ndim != 3 or x.shape[0] != M or x.shape[2] != d:
+                raise ValueError(f"expected (M, n, d) input with M={M}, d={d}")
+            return torch.stack([getattr(p, what)(x[t].contiguous()) for t, p in enumerate(self.pdfs)])
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 3 or x.shape[0] != M or x.shape[2] != d:
+            raise ValueError(f"expected (M, n, d) input with M={M}, d={d}")
+        return np.stack([np.asarray(getattr(p, what)(x[t])) for t, p in enumerate(self.pdfs)])
+
+    @counted
+    def log_prob(self, x):
+        """x (M, n, d) -> (M, n): member t's log_prob of its own rows x[t], each evaluated on the device."""
+        return self._per_member(x, "_log_prob_device")
+
+    @counted
+    def gradient(self, x):
+        """x (M, n, d) -> (M, n, d): member t's gradient (as its class defines it) at its own rows, on the device."""
+        return self._per_member(x, "_gradient_device")
 
 
 class Bingham(Distribution):

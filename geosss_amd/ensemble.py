@@ -74,11 +74,30 @@ def reduce_sum(t, group=None):
     return t
 
 
+def batch_chains_per_target(distribution, n_total, lo, hi):
+    """None for an ordinary target.  A TargetBatch: m = n_total / len(batch), and the shard [lo, hi) must be a run of whole
+    targets -- a shard that cuts a target's block of chains is refused."""
+    from .distributions import TargetBatch
+    if not isinstance(distribution, TargetBatch):
+        return None
+    M = len(distribution)
+    if n_total % M:
+        raise ValueError(f"a TargetBatch of {M} targets needs a multiple of {M} chains (got {n_total})")
+    m = n_total // M
+    if lo % m or hi % m:
+        raise ValueError(f"the shard of chains [{lo}, {hi}) cuts a target's block of {m} chains: choose the number of targets a "
+                         "multiple of the number of ranks")
+    return m
+
+
 def sharded_sampler(cls, distribution, n_total, seed, d=None, init_seed=0, **kwargs):
     """Build this rank's sampler for an ensemble of n_total chains with uniform initial states:
     chain ids and initial states are those of the unsharded ensemble restricted to the shard."""
     from .sphere import sample_sphere_device
     lo, hi = shard_bounds(n_total)
     d = d or distribution.d
+    batch_m = batch_chains_per_target(distribution, n_total, lo, hi)
+    if batch_m is not None:
+        kwargs["chains_per_target"] = batch_m
     x0 = sample_sphere_device(d - 1, hi - lo, seed=init_seed, chain_offset=lo, device=kwargs.get("device"))
     return cls(distribution, x0.t(), seed, chain_offset=lo, **kwargs)

@@ -36,6 +36,7 @@ import contextlib
 import os
 
 from . import _lib, _pinned
+from .distributions import TargetBatch
 from .sphere import _device_index, current_stream_ptr
 
 __all__ = ["determine_burnin", "RejectionSphericalSliceSampler", "ShrinkageSphericalSliceSampler", "MetropolisHastings",
@@ -142,7 +143,10 @@ class RejectionSphericalSliceSampler:
     _sampler = _lib.REJECT
 
     def __init__(self, distribution, initial_state, seed=None, *, device=None, mode="auto", max_tries=None,
-                 chain_offset=0, step_offset=0, variant=0, rng="philox", placement="auto", screen=True):
+                 chain_offset=0, step_offset=0, variant=0, rng="philox", placement="auto", screen=True, chains_per_target=None):
+        """chains_per_target: for a TargetBatch only -- m, the chains each target owns.  Default: n_chains / len(batch), which
+        must divide exactly; a sampler that covers a run of the batch's targets only (chain_offset = t0 m, e.g. a shard)
+        passes m itself."""
         if rng not in ("philox", "numpy"):
             raise ValueError("rng must be 'philox' or 'numpy'")
         if placement not in ("auto", "packed", "spread"):
@@ -151,6 +155,12 @@ class RejectionSphericalSliceSampler:
         if many_seeds and rng != "numpy":
             raise ValueError("a list of seeds (one numpy generator per chain) needs rng='numpy'; the Philox stream "
                              "takes one seed and keys every chain by its global chain id")
+        # a TargetBatch: m and the refusals that need no device, before anything touches one
+        self._batch_m = None
+        if isinstance(distribution, TargetBatch):
+            self._batch_m = self._plan_batch(distribution, initial_state, chains_per_target, rng, int(chain_offset))
+        elif chains_per_target is not None:
+            raise ValueError("chains_per_target belongs to a TargetBatch")
         _lib.require_device()
         self._lib = _lib.load()
         self.target = distribution
@@ -172,8 +182,14 @@ class RejectionSphericalSliceSampler:
         # default kernel with its screen's verdicts ignored where it can (GSSS_VARIANT_FAST_VERIFY: must give the same bits)
         self.screen = screen if screen == "verify" else bool(screen)
         self._step = int(step_offset)
-        self._target_dev = distribution._device_target(self.device)
+        if self._batch_m is not None:
+            self._target_dev = distribution._device_target(self.device, chains_per_target=self._batch_m)
+        else:
+            self._target_dev = distribution._device_target(self.device)
         self._set_state(initial_state)
+        if self._batch_m is not None:
+            self._resolve_batch_mode(mode)
+            mode = self.mode
         if rng == "numpy":
             # a generator per chain, sequential: fast mode serves it where a chain is one lane's (or, small ensembles, one
             # wavefront's) -- the lane-per-chain shapes; the cooperative shapes run the exact kernels
@@ -197,6 +213,57 @@ class RejectionSphericalSliceSampler:
         self._rng_state = self._numpy_states(seed) if rng == "numpy" else None
         self._stats = None
 
+    # ------------------------------------------------------------------ target batches
+    _batch_ok = True   # (the Metropolis-Hastings / HMC classes have no batch kernels)
+
+    def _plan_batch(self, batch, initial_state, chains_per_target, rng, chain_offset):
+        """m for a TargetBatch, and the refusals that need no device: the sampler class, the stream, the divisibility rules."""
+        if not self._batch_ok:
+            raise TypeError(f"{type(self).__name__} does not sample a TargetBatch: the batch kernels are the slice samplers' "
+                            "(ShrinkageSphericalSliceSampler, RejectionSphericalSliceSampler)")
+        if rng != "philox":
+            raise ValueError("a TargetBatch runs on the library stream (rng='philox'): numpy's stream is one generator per chain "
+                             "of one target")
+        n = 1 if np.ndim(initial_state) == 1 else int(np.shape(initial_state)[0])
+        M = len(batch)
+        if chains_per_target is None:
+            if n % M:
+                raise ValueError(f"a TargetBatch of {M} targets needs a multiple of {M} chains, target-major (got {n}); a sampler "
+                                 "on a run of the targets only passes chains_per_target")
+            m = n // M
+        else:
+            m = int(chains_per_target)
+            if m < 1 or n % m:
+                raise ValueError(f"n_chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+        if m < 1:
+            raise ValueError("a TargetBatch needs at least one chain per target")
+        if chain_offset % m:
+            raise ValueError(f"chain_offset ({chain_offset}) must be a multiple of the chains per target ({m}): a sampler "
+                             "starts at a target's first chain")
+        if chain_offset // m + n // m > M:
+            raise ValueError(f"chains {chain_offset} .. {chain_offset + n} reach past the last of the {M} targets "
+                             f"({m} chains per target)")
+        return m
+
+    def _resolve_batch_mode(self, mode):
+        """mode='auto' -> 'fast' where a batch fast kernel serves the shape (with this `screen`), else the exact kernels with
+        the usual warning; mode='fast' without one raises."""
+        if mode == "exact":
+            return
+        if self.screen == "verify":
+            v = _lib.VARIANT_FAST_VERIFY
+        else:
+            v = 0 if self.screen else _lib.VARIANT_FAST_DOUBLE
+        fast_ok = bool(self._lib.gsss_kernel_name(self._target_dev.handle, _lib.MODE_FAST, v, 0)) and not self.variant
+        if mode == "fast":
+            if not fast_ok:
+                raise ValueError("no batch fast kernel serves this TargetBatch (lane-per-chain kernels: d = 3 .. 16; vMF mixtures of up "
+                                 "to 16 terms at d <= 10, 10 beyond); use mode='exact' or 'auto'")
+            return
+        self.mode = "fast" if fast_ok else "exact"
+        if not fast_ok and not self.variant:
+            _warn_exact_fallback(self.target)
+
     # ------------------------------------------------------------------ running statistics
     def enable_stats(self, lags=32, projection=None, hop=None, modes=None, second_moment=None):
         """Accumulate running statistics of the retained series inside the sampler kernels (gsss_run_args.stats_dev):
@@ -209,6 +276,9 @@ class RejectionSphericalSliceSampler:
         a mode are left out).  second_moment: keep the d (d + 1) / 2 sums of x_i x_j too
         (default: for d <= 16; they grow as d^2 -- 20 100 rows per chain at d = 200).  Every slice-sampler kernel family
         accumulates them (lane, lane-group and cooperative layouts)."""
+        if self._batch_m is not None:
+            raise ValueError("running statistics take one set of directions (projection, hop, modes): they are not built for a "
+                             "TargetBatch")
         d = self.d
         w = np.zeros(d) if projection is None else np.asarray(projection, dtype=np.float64)
         if projection is None:
@@ -445,6 +515,8 @@ class RejectionSphericalSliceSampler:
         n_steps = int(n_steps)
         if n_steps < 0:
             raise ValueError("n_steps must be >= 0")
+        if replay is not None and self._batch_m is not None:
+            raise ValueError("a TargetBatch runs on the library stream: replay= is not built for it")
         if replay is not None:
             if not isinstance(replay, torch.Tensor):
                 replay = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(replay), dtype=np.float64))
@@ -576,6 +648,8 @@ class RejectionSphericalSliceSampler:
             block_s = (skip + (n_rows - 1) * thin) * _ROUND_STEP_S
             blocks = int(min(16, nbytes // (32 << 20), copy_s / max(block_s, 1e-6)))
         blocks = max(1, min(int(blocks), n))
+        if self._batch_m is not None:  # a block of chains is a run of whole targets
+            blocks = min(blocks, n // self._batch_m)
         if blocks > 1 and (not self._blockwise or self._stats is not None):
             raise ValueError("this sampler carries per-chain launch state beyond the slice samplers': blocks must be 1")
         return blocks
@@ -616,6 +690,8 @@ class RejectionSphericalSliceSampler:
             main.synchronize()
             return host
         per = -(-n // blocks)
+        if self._batch_m is not None:  # cut at multiples of m only
+            per = -(-per // self._batch_m) * self._batch_m
         bufs = [torch.empty((per, n_rows, d), dtype=torch.float64, device=self._tdev) for _ in range(2)]
         copy = torch.cuda.Stream(dev)
         copied = [None, None]                       # the event after which a buffer may be written again
@@ -650,6 +726,7 @@ class MetropolisHastings(RejectionSphericalSliceSampler):
     own.  Same constructor and attributes as the reference: `.stepsize`, `.n_accept`, `.reset(burnin)`."""
 
     _sampler = _lib.RWMH
+    _batch_ok = False
     _calls_per_step = 2  # log_prob(proposal) and log_prob(state), mcmc.py:152
 
     _blockwise = False  # (per-chain stepsizes, acceptance counters, momenta: sample() runs all chains in one launch sequence)

@@ -248,6 +248,22 @@ int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **o
  * which).  The handle serves every call a target handle serves. */
 int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_components, const double *log_weights, int device,
                                gsss_target **out);
+/* A batch of targets sampled in ONE launch: n_targets descriptors of one family and one shape -- all GSSS_VMF_MIXTURE of one d and
+ * one K, or all GSSS_BINGHAM of one d, all with or all without the linear term b -- packed as gsss_target_create packs each, at an
+ * equal stride in one device allocation.  Target t owns the chains [t m, (t + 1) m) in GLOBAL chain ids, m = chains_per_target:
+ * chain c of a gsss_run call belongs to target (chain_offset + c) / m, so the rule lives in the handle and gsss_run_args is as it
+ * was.  A call covers whole targets: chain_offset and n_chains are multiples of m (any run of targets may be launched, e.g. a
+ * shard of the batch).  Samplers GSSS_SHRINK / GSSS_REJECT on the library (Philox) stream; GSSS_MODE_EXACT in every layout and
+ * placement, GSSS_MODE_FAST one chain per lane at d = 3 .. 16 (screened or all-double; placement is ignored there).  Chains
+ * are the ones n_targets separate handles give, with the same seed and chain_offset = t m, bit for bit -- except that Bingham
+ * members with a diagonal A run the diagonal fast kernels only if EVERY member's A is diagonal.  The screen's scale is the
+ * maximum over the members.  GSSS_E_UNSUPPORTED (gsss_last_error says which): another kind than the two above, members of
+ * different kind, d, K or b-ness; from gsss_run: another sampler, replay_dev, rng_state_dev, stats_dev, a chain_offset or n_chains
+ * that is no multiple of m or reaches past the last target, a shape without a batch fast kernel in GSSS_MODE_FAST; from
+ * gsss_logprob / gsss_gradient always (evaluate the members' own handles).  gsss_kernel_name names the batch builds
+ * ("run_kernel<lane3, VmfMixture, batch>", "screened_kernel<5, ScreenBingham<5>, batch>", ...). */
+int gsss_target_create_batch(const gsss_target_desc *targets, int32_t n_targets, int64_t chains_per_target, int device,
+                             gsss_target **out);
 /* The vector layout (an id of gsss_variant_name's list) the exact kernels run dimension d in: the layout a user module for d must
  * be compiled for (geosss_amd/usertarget.py passes it as -DGSSS_USER_VEC).  < 0: no layout covers d. */
 int gsss_exact_layout(int32_t d);
