@@ -89,74 +89,63 @@ int do_fast_batch(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi
     return launch_kernel("fast batch", kern, grid, lds, st, nullptr, tb, batch_lane_args(rb), bb);
 }
 
-// vMF mixtures, d = 3 .. 10: the component buckets of lane_vmf (gsss_fast_vmf_lane.h) -- screened 3, 4, 6, 10, 16; all-double 4, 16
+// The batch launchers: a switch over the pick (gsss_fast_select.h -- the buckets, and where the batch build departs from the
+// single-target one).  vMF mixtures, d = 3 .. 10: screened 3, 4, 6, 10, 16; all-double 4, 16
 template <int D>
-int batch_lane_vmf(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, FastProbe *probe, hipStream_t st)
+int batch_lane_vmf(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
 {
-    const int ks = tb.k <= 3 ? 3 : (tb.k <= 4 ? 4 : (tb.k <= 6 ? 6 : (tb.k <= 10 ? 10 : 16)));
-    const int kf = tb.k <= 4 ? 4 : 16;
-    const bool screen = rb.screen && tb.scale <= kScreenMaxKappa;
-    if (probe) {
-        if (screen) GSSS_PROBE(true, "screened_kernel<%d, ScreenVmf<%d, %d>, batch>", D, D, ks);
-        GSSS_PROBE(true, "fast_kernel<%d, FastVmf<%d, %d>, batch>", D, D, kf);
+    if (p.family == kFamScreened) {
+        switch (p.kc) {
+        case 3: return do_screened_batch<D, ScreenVmf<D, 3>>(tb, rb, bi, st);
+        case 4: return do_screened_batch<D, ScreenVmf<D, 4>>(tb, rb, bi, st);
+        case 6: return do_screened_batch<D, ScreenVmf<D, 6>>(tb, rb, bi, st);
+        case 10: return do_screened_batch<D, ScreenVmf<D, 10>>(tb, rb, bi, st);
+        case 16: return do_screened_batch<D, ScreenVmf<D, 16>>(tb, rb, bi, st);
+        }
+    } else if (p.family == kFamFast) {
+        if (p.kc == 4) return do_fast_batch<D, FastVmf<D, 4>>(tb, rb, bi, st);
+        if (p.kc == 16) return do_fast_batch<D, FastVmf<D, 16>>(tb, rb, bi, st);
     }
-    if (!screen) return kf == 4 ? do_fast_batch<D, FastVmf<D, 4>>(tb, rb, bi, st) : do_fast_batch<D, FastVmf<D, 16>>(tb, rb, bi, st);
-    switch (ks) {
-    case 3: return do_screened_batch<D, ScreenVmf<D, 3>>(tb, rb, bi, st);
-    case 4: return do_screened_batch<D, ScreenVmf<D, 4>>(tb, rb, bi, st);
-    case 6: return do_screened_batch<D, ScreenVmf<D, 6>>(tb, rb, bi, st);
-    case 10: return do_screened_batch<D, ScreenVmf<D, 10>>(tb, rb, bi, st);
-    default: return do_screened_batch<D, ScreenVmf<D, 16>>(tb, rb, bi, st);
-    }
+    return pick_error(p);
 }
-// d = 11 .. 16, K <= 10: the screened kernel in the buckets 3, 6, 10 (lane_vmf_wide); all-double (screen off, or kappa beyond the
-// screen's reach) the buckets 4 and 10 of fast_kernel, which a single target has no lane build of at these d (bucket 16, the
-// one of d <= 10, spills at d >= 14: 256 registers and 760 .. 1208 bytes of scratch a lane; bucket 10 takes 199 at d = 16)
+// d = 11 .. 16, K <= 10: screened 3, 6, 10; all-double 4, 10
 template <int D>
-int batch_lane_vmf_wide(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, FastProbe *probe, hipStream_t st)
+int batch_lane_vmf_wide(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
 {
-    const int ks = tb.k <= 3 ? 3 : (tb.k <= 6 ? 6 : 10);
-    const int kf = tb.k <= 4 ? 4 : 10;
-    const bool screen = rb.screen && tb.scale <= kScreenMaxKappa;
-    if (probe) {
-        if (screen) GSSS_PROBE(true, "screened_kernel<%d, ScreenVmf<%d, %d>, batch>", D, D, ks);
-        GSSS_PROBE(true, "fast_kernel<%d, FastVmf<%d, %d>, batch>", D, D, kf);
+    if (p.family == kFamScreened) {
+        if (p.kc == 3) return do_screened_batch<D, ScreenVmf<D, 3>>(tb, rb, bi, st);
+        if (p.kc == 6) return do_screened_batch<D, ScreenVmf<D, 6>>(tb, rb, bi, st);
+        if (p.kc == 10) return do_screened_batch<D, ScreenVmf<D, 10>>(tb, rb, bi, st);
+    } else if (p.family == kFamFast) {
+        if (p.kc == 4) return do_fast_batch<D, FastVmf<D, 4>>(tb, rb, bi, st);
+        if (p.kc == 10) return do_fast_batch<D, FastVmf<D, 10>>(tb, rb, bi, st);
     }
-    if (!screen) return kf == 4 ? do_fast_batch<D, FastVmf<D, 4>>(tb, rb, bi, st) : do_fast_batch<D, FastVmf<D, 10>>(tb, rb, bi, st);
-    if (ks == 3) return do_screened_batch<D, ScreenVmf<D, 3>>(tb, rb, bi, st);
-    if (ks == 6) return do_screened_batch<D, ScreenVmf<D, 6>>(tb, rb, bi, st);
-    return do_screened_batch<D, ScreenVmf<D, 10>>(tb, rb, bi, st);
+    return pick_error(p);
 }
-// Bingham / Fisher-Bingham: the compact diagonal target when every member's A is diagonal and none has a linear term (tb.k == 1)
+// Bingham / Fisher-Bingham, d = 3 .. 16
 template <int D>
-int batch_lane_bingham(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, FastProbe *probe, hipStream_t st)
+int batch_lane_bingham(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
 {
-    const bool compact = tb.k == 1;
-    if (probe) {
-        if (rb.screen && compact) GSSS_PROBE(true, "screened_kernel<%d, ScreenBinghamDiag<%d>, batch>", D, D);
-        if (rb.screen) GSSS_PROBE(true, "screened_kernel<%d, ScreenBingham<%d>, batch>", D, D);
-        GSSS_PROBE(true, "fast_kernel<%d, FastBingham<%d>, batch>", D, D);
-    }
-    if (!rb.screen) return do_fast_batch<D, FastBingham<D>>(tb, rb, bi, st);
-    if (compact) return do_screened_batch<D, ScreenBinghamDiag<D>>(tb, rb, bi, st);
+    if (p.family == kFamFast) return do_fast_batch<D, FastBingham<D>>(tb, rb, bi, st);
+    if (p.family != kFamScreened) return pick_error(p);
+    if (p.flavour == kFlavBinghamDiag) return do_screened_batch<D, ScreenBinghamDiag<D>>(tb, rb, bi, st);
     return do_screened_batch<D, ScreenBingham<D>>(tb, rb, bi, st);
 }
 
 #define GSSS_BATCH_LANE_DIMS(X) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
 #define GSSS_BATCH_WIDE_DIMS(X) X(11) X(12) X(13) X(14) X(15) X(16)
 #define GSSS_DECLARE(D) \
-    extern template int batch_lane_vmf<D>(const TargetBlock &, const RunBlock &, const BatchInfo &, FastProbe *, hipStream_t); \
-    extern template int batch_lane_bingham<D>(const TargetBlock &, const RunBlock &, const BatchInfo &, FastProbe *, hipStream_t);
+    extern template int batch_lane_vmf<D>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t); \
+    extern template int batch_lane_bingham<D>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t);
 GSSS_BATCH_LANE_DIMS(GSSS_DECLARE)
 #undef GSSS_DECLARE
 #define GSSS_DECLARE(D) \
-    extern template int batch_lane_vmf_wide<D>(const TargetBlock &, const RunBlock &, const BatchInfo &, FastProbe *, hipStream_t); \
-    extern template int batch_lane_bingham<D>(const TargetBlock &, const RunBlock &, const BatchInfo &, FastProbe *, hipStream_t);
+    extern template int batch_lane_vmf_wide<D>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t); \
+    extern template int batch_lane_bingham<D>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t);
 GSSS_BATCH_WIDE_DIMS(GSSS_DECLARE)
 #undef GSSS_DECLARE
 
-// probe != nullptr: launch nothing, only answer whether a batch kernel exists and name it (as the launch_fast_* entry points do)
-int launch_batch_fast_vmf(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, FastProbe *probe, hipStream_t st);
-int launch_batch_fast_bingham(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, FastProbe *probe, hipStream_t st);
+int launch_batch_fast_vmf(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st);
+int launch_batch_fast_bingham(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st);
 
 }  // namespace gsss

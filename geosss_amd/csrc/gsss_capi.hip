@@ -374,19 +374,6 @@ int launch_cpd_mh(int variant, int draws, int sampler, const TargetBlock &tb, co
 int launch_cpd_logprob(int variant, const TargetBlock &tb, const double *x, int64_t n, double *out, bool grad, hipStream_t st);
 }  // namespace gsss
 
-static int fast_dispatch(const gsss::TargetBlock &tb, const gsss::RunBlock &rb, bool replay, gsss::FastProbe *probe,
-                         hipStream_t st)
-{
-    switch (tb.kind) {
-    case GSSS_VMF_MIXTURE: return gsss::launch_fast_vmf(tb, rb, replay, probe, st);
-    case GSSS_BINGHAM: return gsss::launch_fast_bingham(tb, rb, replay, probe, st);
-    case GSSS_CURVE_VMF: return gsss::launch_fast_curve(tb, rb, replay, probe, st);
-    case GSSS_MIXTURE: return gsss::launch_fast_mixture(tb, rb, replay, probe, st);
-    }
-    if (!probe) gsss::set_error("fast mode is not built for target kind %d", tb.kind);
-    return GSSS_E_UNSUPPORTED;
-}
-
 // ==========================================================================================
 // extern "C"
 // ==========================================================================================
@@ -404,19 +391,93 @@ struct gsss_target {
 
 static bool is_batch(const gsss_target *t) { return t->batch.n_targets > 0; }
 
-static int batch_fast_dispatch(const gsss::TargetBlock &tb, const gsss::RunBlock &rb, const gsss::BatchInfo &bi, gsss::FastProbe *probe,
-                               hipStream_t st)
+// The ask of a fast-mode launch (gsss_fast_select.h): the target's shape and the launch's traits.  The two environment switches
+// that take part in the selection are read here, so that fast_select itself reads nothing.
+static FastAsk fast_ask(const gsss_target *t, int screen, bool spread, bool numpy = false, bool replay = false, bool stats = false)
 {
-    if (tb.kind == GSSS_VMF_MIXTURE) return gsss::launch_batch_fast_vmf(tb, rb, bi, probe, st);
-    return gsss::launch_batch_fast_bingham(tb, rb, bi, probe, st);
+    const TargetBlock &tb = t->tb;
+    FastAsk a{};
+    a.kind = tb.kind;
+    a.d = tb.d;
+    a.k = tb.k;
+    if (tb.kind == GSSS_MIXTURE) {
+        const MixInfo mi = mix_info(tb);
+        a.k = mi.terms;
+        a.mix_curve = mi.curve;
+    }
+    a.scale = tb.scale;
+    a.screen = screen;
+    a.spread = spread;
+    a.numpy = numpy;
+    a.replay = replay;
+    a.stats = stats;
+    a.batch = is_batch(t);
+    a.curve_tail = 1;
+    if (tb.kind == GSSS_CURVE_VMF) {
+        static const bool two = [] {
+            const char *e = getenv("GSSS_CURVE_L2");
+            return e && e[0] == '1';
+        }();
+        const char *env_tail = getenv("GSSS_CURVE_TAIL");  // (read per launch: tests switch it)
+        a.curve_l2 = two;
+        a.curve_tail = env_tail ? atoi(env_tail) : 1;
+    }
+    return a;
+}
+
+// fast_select refused the shape: say which
+static int fast_refused(const gsss_target *t)
+{
+    const TargetBlock &tb = t->tb;
+    if (is_batch(t) && tb.kind == GSSS_VMF_MIXTURE)
+        set_error("fast mode is not built for a batch of vMF mixtures with d=%d, K=%d: the batch kernels are the lane-per-chain ones "
+                  "(d = 3 .. 10 with K <= 16; d = 11 .. 16 with K <= 10); use GSSS_MODE_EXACT", tb.d, tb.k);
+    else if (is_batch(t))
+        set_error("fast mode is not built for a batch of Bingham targets with d=%d: the batch kernels are the lane-per-chain ones "
+                  "(d = 3 .. 16); use GSSS_MODE_EXACT", tb.d);
+    else if (tb.kind == GSSS_VMF_MIXTURE)
+        set_error("fast mode is not built for a vMF mixture with d=%d, K=%d", tb.d, tb.k);
+    else if (tb.kind == GSSS_BINGHAM)
+        set_error("fast mode is not built for a Bingham target with d=%d", tb.d);
+    else if (tb.kind == GSSS_CURVE_VMF)
+        set_error("fast mode is not built for a curve-vMF target with d=%d, %d knots", tb.d, tb.k);
+    else if (tb.kind == GSSS_MIXTURE) {
+        const MixInfo mi = mix_info(tb);
+        set_error("fast mode is not built for this mixture (d=%d, %d terms%s): d = 3 .. 16, at most %d vMF / Bingham terms, "
+                  "no curve component", tb.d, mi.terms, mi.curve ? ", a curve component" : "", kMixFastTerms);
+    } else
+        set_error("fast mode is not built for target kind %d", tb.kind);
+    return GSSS_E_UNSUPPORTED;
+}
+
+// the pick goes to its family's launcher (tb: the target, or the launch's first member of a batch)
+static int fast_launch(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, bool replay, hipStream_t st)
+{
+    if (p.batch)
+        return tb.kind == GSSS_VMF_MIXTURE ? launch_batch_fast_vmf(p, tb, rb, bi, st) : launch_batch_fast_bingham(p, tb, rb, bi, st);
+    switch (tb.kind) {
+    case GSSS_VMF_MIXTURE: return launch_fast_vmf(p, tb, rb, replay, st);
+    case GSSS_BINGHAM: return launch_fast_bingham(p, tb, rb, replay, st);
+    case GSSS_CURVE_VMF: return launch_fast_curve(p, tb, rb, replay, st);
+    case GSSS_MIXTURE: return launch_fast_mixture(p, tb, rb, replay, st);
+    }
+    return pick_error(p);
 }
 
 // The parameter blob of one target (layout per kind: TargetBlock::blob); gsss_target_create, and per component
 // gsss_target_create_mixture
-static int pack_target(const gsss_target_desc *desc, std::vector<double> &blob, bool &bingham_diagonal, double &scale,
-                       int &cpd_variant)
+struct PackedTarget {
+    std::vector<double> blob;
+    bool bingham_diagonal = false;  // GSSS_BINGHAM: A is diagonal
+    double scale = 0.0;             // TargetBlock::scale
+    int cpd_variant = 0;
+};
+
+static int pack_target(const gsss_target_desc *desc, PackedTarget &out)
 {
     const int d = desc->d, k = desc->k;
+    std::vector<double> &blob = out.blob;
+    double &scale = out.scale;
     switch (desc->kind) {
     case GSSS_VMF_MIXTURE:
         if (k < 1 || !desc->mu || !desc->logc) {
@@ -449,7 +510,7 @@ static int pack_target(const gsss_target_desc *desc, std::vector<double> &blob, 
                         diag = false;
                         break;
                     }
-            bingham_diagonal = diag;
+            out.bingham_diagonal = diag;
         }
         break;
     case GSSS_CURVE_VMF: {
@@ -505,13 +566,49 @@ static int pack_target(const gsss_target_desc *desc, std::vector<double> &blob, 
         blob.push_back((double)kn);
         blob.push_back(0.0);
         blob.push_back(0.0);
-        cpd_variant = (kn <= 8 ? 0 : 2) + (uniform ? 0 : 1);
+        out.cpd_variant = (kn <= 8 ? 0 : 2) + (uniform ? 0 : 1);
         break;
     }
     default:
         set_error("unknown target kind %d", desc->kind);
         return GSSS_E_INVALID;
     }
+    return GSSS_OK;
+}
+
+// TargetBlock::k of a Bingham target holds flags: bit 0 a diagonal A, bit 1 a linear term (BinghamFisher)
+static int bingham_flags(bool diagonal, const gsss_target_desc *desc) { return (diagonal ? 1 : 0) | (desc->mu ? 2 : 0); }
+
+// The one upload path of the target creators: `n` doubles at `host` go to `device`, and *out becomes a copy of `proto` (the
+// creator's filled-in handle: TargetBlock, cpd_variant, user, batch) that owns them.  Called after every argument was checked:
+// nothing before it touches the device.
+static int upload_target(const double *host, size_t n, int device, const gsss_target &proto, gsss_target **out)
+{
+    int ndev = gsss_device_count();
+    if (ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("device %d not available (%d HIP devices visible)", device, ndev);
+        return GSSS_E_NO_DEVICE;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    gsss_target *t = new (std::nothrow) gsss_target(proto);
+    if (!t) {
+        set_error("out of host memory");
+        return GSSS_E_INVALID;
+    }
+    t->device = device;
+    t->blob_doubles = n;
+    t->blob_dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), (n > 0 ? n : 1) * sizeof(double));
+    if (e == hipSuccess && n > 0) e = hipMemcpy(t->blob_dev, host, n * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error("copying target parameters failed: %s", hipGetErrorString(e));
+        if (t->blob_dev) (void)hipFree(t->blob_dev);
+        delete t;
+        return GSSS_E_HIP;
+    }
+    t->tb.blob = t->blob_dev;
+    *out = t;
     return GSSS_OK;
 }
 
@@ -544,45 +641,17 @@ int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **o
         return GSSS_E_INVALID;
     }
     if (select_vec(d, 0) < 0) return GSSS_E_UNSUPPORTED;  // before any parameter array is touched
-    std::vector<double> blob;
-    bool bingham_diagonal = false;
-    double scale = 0.0;
-    int cpd_variant = 0;
-    if (int rc = pack_target(desc, blob, bingham_diagonal, scale, cpd_variant)) return rc;
-    int ndev = gsss_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("device %d not available (%d HIP devices visible)", device, ndev);
-        return GSSS_E_NO_DEVICE;
-    }
-    DeviceGuard guard(device);
-    if (!guard.ok) return GSSS_E_HIP;
-    gsss_target *t = new (std::nothrow) gsss_target();
-    if (!t) {
-        set_error("out of host memory");
-        return GSSS_E_INVALID;
-    }
-    t->device = device;
-    t->blob_doubles = blob.size();
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), blob.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(t->blob_dev, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("copying target parameters failed: %s", hipGetErrorString(e));
-        if (t->blob_dev) (void)hipFree(t->blob_dev);
-        delete t;
-        return GSSS_E_HIP;
-    }
-    t->tb.blob = t->blob_dev;
-    t->tb.kind = desc->kind;
-    t->tb.d = d;
-    // Bingham: k holds flags -- bit 0 a diagonal A, bit 1 a linear term (BinghamFisher)
-    t->tb.k = desc->kind == GSSS_BINGHAM ? ((bingham_diagonal ? 1 : 0) | (desc->mu ? 2 : 0)) : k;
-    if (desc->kind == GSSS_CPD) t->tb.k = k | (desc->n_target << 16);       // registration: both cloud sizes
-    t->cpd_variant = cpd_variant;
-    t->tb.dpad = 0;
-    t->tb.kappa = desc->kappa;
-    t->tb.scale = scale;
-    *out = t;
-    return GSSS_OK;
+    PackedTarget pk;
+    if (int rc = pack_target(desc, pk)) return rc;
+    gsss_target proto{};
+    proto.tb.kind = desc->kind;
+    proto.tb.d = d;
+    proto.tb.k = desc->kind == GSSS_BINGHAM ? bingham_flags(pk.bingham_diagonal, desc) : k;
+    if (desc->kind == GSSS_CPD) proto.tb.k = k | (desc->n_target << 16);  // registration: both cloud sizes
+    proto.tb.kappa = desc->kappa;
+    proto.tb.scale = pk.scale;
+    proto.cpd_variant = pk.cpd_variant;
+    return upload_target(pk.blob.data(), pk.blob.size(), device, proto, out);
 }
 
 int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_components, const double *log_weights, int device,
@@ -636,16 +705,15 @@ int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_com
     double scale_all = 0.0;
     for (int c = 0; c < n_components; ++c) {
         const gsss_target_desc *desc = components + c;
-        std::vector<double> part;
-        bool diagonal = false;
-        double scale = 0.0;
-        int cpd_variant = 0;
-        if (int rc = pack_target(desc, part, diagonal, scale, cpd_variant)) {
+        PackedTarget pk;
+        if (int rc = pack_target(desc, pk)) {
             std::string msg = g_err;
             set_error("component %d: %s", c, msg.c_str());
             return rc;
         }
-        const int k = desc->kind == GSSS_BINGHAM ? ((diagonal ? 1 : 0) | (desc->mu ? 2 : 0)) : desc->k;
+        const std::vector<double> &part = pk.blob;
+        const double scale = pk.scale;
+        const int k = desc->kind == GSSS_BINGHAM ? bingham_flags(pk.bingham_diagonal, desc) : desc->k;
         double *h = blob.data() + 1 + (size_t)c * kMixHeader;
         h[0] = (double)desc->kind;
         h[1] = (double)k;
@@ -679,38 +747,14 @@ int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_com
                   kMixMaxRows, (long long)rows);
         return GSSS_E_UNSUPPORTED;
     }
-    int ndev = gsss_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("device %d not available (%d HIP devices visible)", device, ndev);
-        return GSSS_E_NO_DEVICE;
-    }
-    DeviceGuard guard(device);
-    if (!guard.ok) return GSSS_E_HIP;
-    gsss_target *t = new (std::nothrow) gsss_target();
-    if (!t) {
-        set_error("out of host memory");
-        return GSSS_E_INVALID;
-    }
-    t->device = device;
-    t->blob_doubles = blob.size();
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), blob.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(t->blob_dev, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("copying target parameters failed: %s", hipGetErrorString(e));
-        if (t->blob_dev) (void)hipFree(t->blob_dev);
-        delete t;
-        return GSSS_E_HIP;
-    }
-    t->tb.blob = t->blob_dev;
-    t->tb.kind = GSSS_MIXTURE;
-    t->tb.d = d;
-    t->tb.k = mix_pack_k(n_components, nb, (int)(terms < 255 ? terms : 255), curve);  // (mix_info)
-    t->tb.dpad = (int32_t)rows;
-    t->tb.kappa = (double)extra;
-    t->tb.scale = scale_all;
-    t->cpd_variant = 0;
-    *out = t;
-    return GSSS_OK;
+    gsss_target proto{};
+    proto.tb.kind = GSSS_MIXTURE;
+    proto.tb.d = d;
+    proto.tb.k = mix_pack_k(n_components, nb, (int)(terms < 255 ? terms : 255), curve);  // (mix_info)
+    proto.tb.dpad = (int32_t)rows;
+    proto.tb.kappa = (double)extra;
+    proto.tb.scale = scale_all;
+    return upload_target(blob.data(), blob.size(), device, proto, out);
 }
 
 int gsss_target_create_batch(const gsss_target_desc *targets, int32_t n_targets, int64_t chains_per_target, int device,
@@ -765,15 +809,13 @@ int gsss_target_create_batch(const gsss_target_desc *targets, int32_t n_targets,
                       targets[0].mu ? "has one" : "has none", t, desc->mu ? "has one" : "has none");
             return GSSS_E_UNSUPPORTED;
         }
-        std::vector<double> part;
-        bool diagonal = false;
-        double scale = 0.0;
-        int cpd_variant = 0;
-        if (int rc = pack_target(desc, part, diagonal, scale, cpd_variant)) {
+        PackedTarget pk;
+        if (int rc = pack_target(desc, pk)) {
             std::string msg = g_err;
             set_error("member %d: %s", t, msg.c_str());
             return rc;
         }
+        const std::vector<double> &part = pk.blob;
         if (t == 0) {
             stride = part.size();
             all.reserve(stride * (size_t)n_targets);
@@ -783,43 +825,17 @@ int gsss_target_create_batch(const gsss_target_desc *targets, int32_t n_targets,
             return GSSS_E_INVALID;
         }
         all.insert(all.end(), part.begin(), part.end());
-        all_diagonal = all_diagonal && diagonal;
-        scale_all = std::fmax(scale_all, scale);
+        all_diagonal = all_diagonal && pk.bingham_diagonal;
+        scale_all = std::fmax(scale_all, pk.scale);
     }
-    int ndev = gsss_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("device %d not available (%d HIP devices visible)", device, ndev);
-        return GSSS_E_NO_DEVICE;
-    }
-    DeviceGuard guard(device);
-    if (!guard.ok) return GSSS_E_HIP;
-    gsss_target *t = new (std::nothrow) gsss_target();
-    if (!t) {
-        set_error("out of host memory");
-        return GSSS_E_INVALID;
-    }
-    t->device = device;
-    t->blob_doubles = all.size();
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), all.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(t->blob_dev, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("copying target parameters failed: %s", hipGetErrorString(e));
-        if (t->blob_dev) (void)hipFree(t->blob_dev);
-        delete t;
-        return GSSS_E_HIP;
-    }
-    t->tb.blob = t->blob_dev;
-    t->tb.kind = kind;
-    t->tb.d = d;
+    gsss_target proto{};
+    proto.tb.kind = kind;
+    proto.tb.d = d;
     // Bingham: the flags of gsss_target_create -- the diagonal kernels only if EVERY member's A is diagonal
-    t->tb.k = kind == GSSS_BINGHAM ? ((all_diagonal ? 1 : 0) | (targets[0].mu ? 2 : 0)) : k;
-    t->tb.dpad = 0;
-    t->tb.kappa = 0.0;
-    t->tb.scale = scale_all;
-    t->cpd_variant = 0;
-    t->batch = BatchInfo{n_targets, (int64_t)stride, chains_per_target};
-    *out = t;
-    return GSSS_OK;
+    proto.tb.k = kind == GSSS_BINGHAM ? bingham_flags(all_diagonal, targets) : k;
+    proto.tb.scale = scale_all;
+    proto.batch = BatchInfo{n_targets, (int64_t)stride, chains_per_target};
+    return upload_target(all.data(), all.size(), device, proto, out);
 }
 
 int gsss_exact_layout(int32_t d)
@@ -863,40 +879,12 @@ int gsss_target_create_user(const void *table, int32_t d, const double *params, 
         set_error("a user target takes at most 2^31-1 parameters");
         return GSSS_E_UNSUPPORTED;
     }
-    int ndev = gsss_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("device %d not available (%d HIP devices visible)", device, ndev);
-        return GSSS_E_NO_DEVICE;
-    }
-    DeviceGuard guard(device);
-    if (!guard.ok) return GSSS_E_HIP;
-    gsss_target *t = new (std::nothrow) gsss_target();
-    if (!t) {
-        set_error("out of host memory");
-        return GSSS_E_INVALID;
-    }
-    t->device = device;
-    t->blob_doubles = (size_t)n_params;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->blob_dev), (n_params > 0 ? (size_t)n_params : 1) * sizeof(double));
-    if (e == hipSuccess && n_params > 0)
-        e = hipMemcpy(t->blob_dev, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("copying target parameters failed: %s", hipGetErrorString(e));
-        if (t->blob_dev) (void)hipFree(t->blob_dev);
-        delete t;
-        return GSSS_E_HIP;
-    }
-    t->tb.blob = t->blob_dev;
-    t->tb.kind = GSSS_USER;
-    t->tb.d = d;
-    t->tb.k = (int32_t)n_params;
-    t->tb.dpad = 0;
-    t->tb.kappa = 0.0;
-    t->tb.scale = 0.0;
-    t->cpd_variant = 0;
-    t->user = m;
-    *out = t;
-    return GSSS_OK;
+    gsss_target proto{};
+    proto.tb.kind = GSSS_USER;
+    proto.tb.d = d;
+    proto.tb.k = (int32_t)n_params;
+    proto.user = m;
+    return upload_target(params, (size_t)n_params, device, proto, out);
 }
 
 int gsss_target_destroy(gsss_target *t)
@@ -1109,27 +1097,30 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
                 set_error("fast mode takes at most 2^31-1 steps / chains per call");
                 return GSSS_E_INVALID;
             }
-            return batch_fast_dispatch(tbb, rb, t->batch, nullptr, st);
+            FastPick pick;
+            if (fast_select(fast_ask(t, rb.screen, false), pick) != GSSS_OK) return fast_refused(t);
+            return fast_launch(pick, tbb, rb, t->batch, false, st);
         }
         return tbb.kind == GSSS_VMF_MIXTURE ? launch_batch_run_vmf(vec, tbb, rb, t->batch, st)
                                             : launch_batch_run_bingham(vec, tbb, rb, t->batch, st);
     }
     const int draws = replay ? kDrawsReplay : (a->rng_state_dev ? kDrawsNumpy : kDrawsPhilox);
-    if (a->mode == GSSS_MODE_FAST && a->rng_state_dev) {  // a generator per chain: the lane-per-chain shapes only
-        FastProbe pr;
-        if (fast_dispatch(t->tb, rb, false, &pr, nullptr) != GSSS_OK || !pr.lane) {
+    if (a->mode == GSSS_MODE_FAST) {
+        FastPick pick;
+        const bool numpy = a->rng_state_dev != nullptr;
+        const int served = fast_select(fast_ask(t, rb.screen, rb.spread != 0, numpy, replay, rb.stats != nullptr), pick);
+        if (numpy && (served != GSSS_OK || !pick.lane)) {  // a generator per chain: the lane-per-chain shapes only
             set_error("in fast mode the numpy stream is served by the lane-per-chain kernels only (gsss_variant_name: "
                       "\"fast-lane\"); use GSSS_MODE_EXACT");
             return GSSS_E_UNSUPPORTED;
         }
-    }
-    if (a->mode == GSSS_MODE_FAST) {
         if (a->n_steps > 0x7FFFFFFFll || a->thin > 0x7FFFFFFFll || a->n_chains > 0x7FFFFFFFll - 1024 ||
             a->replay_stride > 0x7FFFFFFFll) {
             set_error("fast mode takes at most 2^31-1 steps / chains per call");
             return GSSS_E_INVALID;
         }
-        return fast_dispatch(t->tb, rb, replay, nullptr, st);
+        if (served != GSSS_OK) return fast_refused(t);
+        return fast_launch(pick, t->tb, rb, t->batch, replay, st);
     }
     if (mh) {
         if (a->rng_state_dev && (a->sampler == GSSS_RWMH || a->sampler == GSSS_MIX) && t->tb.d < 3) {
@@ -1202,14 +1193,9 @@ int gsss_mode_supported(const gsss_target *t, int32_t mode)
 {
     if (!t) return 0;
     if (mode == GSSS_MODE_EXACT) return select_vec(t->tb.d, 0) >= 0;
-    if (mode == GSSS_MODE_FAST) {
-        FastProbe pr;
-        if (is_batch(t)) {  // (every shape with a batch fast kernel has the screened and the all-double one)
-            RunBlock rbp{};
-            rbp.screen = 1;
-            return batch_fast_dispatch(t->tb, rbp, t->batch, &pr, nullptr) == GSSS_OK;
-        }
-        return fast_dispatch(t->tb, RunBlock{}, false, &pr, nullptr) == GSSS_OK;
+    if (mode == GSSS_MODE_FAST) {  // (every shape with a batch fast kernel has the screened and the all-double one)
+        FastPick pick;
+        return fast_select(fast_ask(t, is_batch(t) ? 1 : 0, false), pick) == GSSS_OK;
     }
     return 0;
 }
@@ -1218,14 +1204,9 @@ const char *gsss_variant_name(const gsss_target *t, int32_t mode, int32_t varian
 {
     if (!t) return "";
     if (mode == GSSS_MODE_FAST) {
-        FastProbe pr;
-        if (is_batch(t)) {
-            RunBlock rbp{};
-            rbp.screen = 1;
-            return batch_fast_dispatch(t->tb, rbp, t->batch, &pr, nullptr) == GSSS_OK ? "fast-lane" : "";
-        }
-        if (fast_dispatch(t->tb, RunBlock{}, false, &pr, nullptr) != GSSS_OK) return "";
-        return pr.lane ? "fast-lane" : "fast-coop";
+        FastPick pick;
+        if (fast_select(fast_ask(t, is_batch(t) ? 1 : 0, false), pick) != GSSS_OK) return "";
+        return pick.lane ? "fast-lane" : "fast-coop";
     }
     const int vec = select_vec_for(t->tb, variant);
     if (vec < 0) return "";
@@ -1241,21 +1222,10 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
     static thread_local char name[200];
     name[0] = 0;
     if (!t) return name;
-    const bool spread = placement == 2;
-    if (mode == GSSS_MODE_FAST) {
-        FastProbe pr;
-        RunBlock rbp{};
-        if (is_batch(t)) {  // one lane per chain whatever the placement
-            rbp.screen = variant == GSSS_VARIANT_FAST_DOUBLE ? 0 : 1;
-            if (batch_fast_dispatch(t->tb, rbp, t->batch, &pr, nullptr) == GSSS_OK) snprintf(name, sizeof(name), "%s", pr.name);
-            return name;
-        }
-        rbp.screen = variant == GSSS_VARIANT_FAST_DOUBLE || spread ? 0 : 1;
-        if (fast_dispatch(t->tb, rbp, false, &pr, nullptr) != GSSS_OK) return name;
-        if (pr.lane && spread && t->tb.d <= 16)
-            snprintf(name, sizeof(name), "wave_kernel%s", strchr(pr.name, '<') ? strchr(pr.name, '<') : "");
-        else
-            snprintf(name, sizeof(name), "%s", pr.name);
+    if (mode == GSSS_MODE_FAST) {  // placement 2: one wavefront per chain (a batch: one lane per chain whatever the placement)
+        const int screen = variant == GSSS_VARIANT_FAST_DOUBLE ? 0 : (variant == GSSS_VARIANT_FAST_VERIFY ? 2 : 1);
+        FastPick pick;
+        if (fast_select(fast_ask(t, screen, placement == 2), pick) == GSSS_OK) fast_name(pick, name, sizeof(name));
         return name;
     }
     const char *vec = gsss_variant_name(t, mode, variant);

@@ -27,6 +27,7 @@
 #include <stdio.h>
 
 #include "gsss_device.h"
+#include "gsss_fast_select.h"
 #include "gsss_math.h"
 
 namespace gsss {
@@ -903,34 +904,35 @@ int do_fast_numpy(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 template <int D, class TP>
 int do_wave(const TargetBlock &tb, const RunBlock &rb, hipStream_t st);
 
-template <int D, class TP>
-int do_fast(const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st)
+// a pick (gsss_fast_select.h) that the launcher it was handed to has no instantiation for: select and the launchers disagree
+inline int pick_error(const FastPick &p)
 {
-    if (replay) return do_fast_run<D, TP, true>(tb, rb, st);
+    char name[160];
+    fast_name(p, name, sizeof(name));
+    set_error("internal error: fast mode selected %s, which its launcher does not build", name);
+    return GSSS_E_INVALID;
+}
+
+// the all-double lane kernels of a pick: fast_kernel in the build of the launch's stream, or wave_kernel (small ensemble: one
+// wavefront per chain)
+template <int D, class TP>
+int do_fast(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st)
+{
     if constexpr (D <= 16) {
-        if (rb.spread) return do_wave<D, TP>(tb, rb, st);  // small ensemble: one wavefront per chain
+        if (p.family == kFamWave) return do_wave<D, TP>(tb, rb, st);
     }
+    if (p.family != kFamFast) return pick_error(p);
+    if (replay) return do_fast_run<D, TP, true>(tb, rb, st);
     if (rb.rng_state != nullptr) return do_fast_numpy<D, TP>(tb, rb, st);  // a generator per chain: one lane per chain
     return do_fast_run<D, TP, false>(tb, rb, st);
 }
 
-// per-target entry points (one translation unit each); GSSS_E_UNSUPPORTED when no instantiation
-// covers (d, k).  `probe` != nullptr: launch nothing, only answer whether a kernel exists and name it.
-struct FastProbe {
-    char name[160];  // the instantiation that would run, e.g. "fast_kernel<3, FastVmf<3, 3>>"
-    bool lane;       // lane-per-chain layout (small ensembles then run wave_kernel of the same shape)
-};
-int launch_fast_vmf(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
-int launch_fast_bingham(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
-int launch_fast_curve(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
-int launch_fast_mixture(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, hipStream_t st);
-int launch_curvespec(const TargetBlock &tb, const RunBlock &rb, bool replay, FastProbe *probe, bool lane, hipStream_t st);
-#define GSSS_PROBE(LANE, ...)                                         \
-    do {                                                              \
-        snprintf(probe->name, sizeof(probe->name), __VA_ARGS__);      \
-        probe->lane = LANE;                                           \
-        return GSSS_OK;                                               \
-    } while (0)
+// per-target launchers (one translation unit each, the lane kernels one per dimension): a switch over the pick's integers
+int launch_fast_vmf(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
+int launch_fast_bingham(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
+int launch_fast_curve(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
+int launch_fast_mixture(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
+int launch_curvespec(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
 
 }  // namespace gsss
 
@@ -947,7 +949,7 @@ constexpr int kCoefRefresh = 64;  // recompute a_i.x from x every this many step
 
 // LDS doubles of a cooperative target's parameters (Bingham's depend on d)
 template <class TP>
-__host__ __device__ inline size_t coop_param_doubles(int d)
+__host__ __device__ constexpr size_t coop_param_doubles(int d)
 {
     if constexpr (TP::kQuadratic)
         return TP::lds_doubles(d);
@@ -1123,7 +1125,7 @@ struct CoopBingham {
     const double *rows;  // unused
     int d;
     bool diagonal;
-    __host__ __device__ static size_t lds_doubles(int d) { return (size_t)(d + 1) * V::DPAD; }
+    __host__ __device__ static constexpr size_t lds_doubles(int d) { return (size_t)(d + 1) * V::DPAD; }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         d = tb.d;

@@ -1,5 +1,5 @@
 // lane-per-chain vMF-mixture kernels at d = 5 (see gsss_fast_vmf_lane.h)
 #include "gsss_fast_vmf_lane.h"
 namespace gsss {
-template int lane_vmf<5>(const TargetBlock &, const RunBlock &, bool, FastProbe *, hipStream_t);
+template int lane_vmf<5>(const FastPick &, const TargetBlock &, const RunBlock &, bool, hipStream_t);
 }

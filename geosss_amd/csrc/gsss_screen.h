@@ -1466,4 +1466,15 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     return launch_kernel("screened", kern, grid, lds, st, plan.ws, tb, rbl);
 }
 
+// the screened lane kernel in the build of the launch's stream (numpy's: where NUMPY says it is built)
+template <int D, class TP, bool NUMPY = true>
+int do_screened(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st)
+{
+    if (rb.rng_state != nullptr) {
+        if constexpr (NUMPY) return do_screened_numpy<D, TP>(tb, rb, st);
+        return pick_error(p);
+    }
+    return replay ? do_screened_run<D, TP, true>(tb, rb, st) : do_screened_run<D, TP, false>(tb, rb, st);
+}
+
 }  // namespace gsss

@@ -46,7 +46,7 @@ def pad_replay(draws, offsets):
     return out
 
 
-# shapes the GSSS_MODE_FAST kernels are built for (geosss_amd/csrc/gsss_fast_*.hip)
+# shapes the GSSS_MODE_FAST kernels are built for: restated by hand from fast_select (geosss_amd/csrc/gsss_fast_select.h)
 FAST_BINGHAM = {3, 4, 5, 6, 7, 8, 9, 10}  # lane kernels; 10 < d <= 128 runs the cooperative one
 
 

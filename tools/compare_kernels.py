@@ -1,14 +1,13 @@
 #!/usr/bin/env python3
-"""Are the kernels of a translation unit the same, instruction for instruction, in two source trees?
-    python tools/compare_kernels.py <other tree> gsss_fast_vmf_d3.hip gsss_fast_bingham.hip
+"""Are the kernels the same, instruction for instruction, in two source trees?
+    python tools/compare_kernels.py <other tree> [gsss_fast_vmf_d3.hip gsss_fast_bingham.hip ...]
 compiles each unit's device code for gfx950 from this tree and from the other one (the build's flags), disassembles both code
-objects with llvm-objdump and compares the function bodies by name.  Two things are normalised: a kernel whose template
-arguments only gained a trailing `false` flag and an empty argument pack is the same kernel, and the literal that follows
-s_getpc_b64 (the pc-relative address of a table) depends on where the object was laid out, not on the kernel.
-The name normalisation is that of ONE change -- the BATCH flag and BatchBlock pack that run_kernel, screened_kernel and fast_kernel
-gained with TargetBatch: a tree with further template parameters reports its kernels as missing, and `replace` below needs the
-new suffix."""
-import os, re, subprocess, sys, tempfile
+objects with llvm-objdump and compares the function bodies by their mangled names.  No unit named: every unit of
+build.sources().  Reported per unit and for the union of the kernels over all units (a kernel may move between units; in the
+union a name counts as different if any of its bodies differs).  Normalised: the literal that follows s_getpc_b64 (the
+pc-relative address of a table) and the padding behind a function depend on where the object was laid out, not on the kernel.  Up to 16 compilations run in
+parallel (--jobs)."""
+import argparse, concurrent.futures as cf, os, re, subprocess, sys, tempfile
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
@@ -29,9 +28,9 @@ def functions(tree, unit, tmp, tag):
     for line in out.splitlines():
         m = re.match(r"^(?:[0-9a-f]+ )?<([^>]+)>:$", line)
         if m:
-            cur = re.sub(r"DpT\d+_$", "", m.group(1).replace("Lb0EJEEEvNS", "EEvNS"))
+            cur = m.group(1)
             d[cur] = []
-        elif cur and line.strip():
+        elif cur and line.strip() and line.strip() != "...":  # ("...": objdump's mark for the zero padding behind a function)
             ins = re.sub(r"\s*//.*$", "", line).strip()
             since_pc = 0 if ins.startswith("s_getpc_b64") else since_pc + 1
             if since_pc in (1, 2) and ins.startswith(("s_add_u32", "s_addc_u32")):
@@ -40,20 +39,45 @@ def functions(tree, unit, tmp, tag):
     return d
 
 
+def report(label, a, b):
+    """a, b: {kernel: body} there and here.  Prints one line (and the offenders), returns how many differ or are missing."""
+    same = [k for k in a if a[k] == b.get(k)]
+    diff = [k for k in a if k in b and a[k] != b[k]]
+    gone = [k for k in a if k not in b]
+    new = [k for k in b if k not in a]
+    print(f"{label}: {len(a)} kernels there, {len(b)} here; identical bodies: {len(same)} ({sum(len(a[k]) for k in same)} "
+          f"instructions), different: {len(diff)}, missing here: {len(gone)}, new here: {len(new)}")
+    for k in diff + gone + new:
+        print("   ", "different" if k in diff else "missing  " if k in gone else "new      ", k)
+    return len(diff) + len(gone) + len(new)
+
+
 def main():
-    other, units = sys.argv[1], sys.argv[2:]
-    bad = 0
-    with tempfile.TemporaryDirectory() as tmp:
-        for unit in units:
-            a, b = functions(other, unit, tmp, "other"), functions(HERE, unit, tmp, "this")
-            same = [k for k in a if a[k] == b.get(k)]
-            diff = [k for k in a if k in b and a[k] != b[k]]
-            gone = [k for k in a if k not in b]
-            bad += len(diff) + len(gone)
-            print(f"{unit}: {len(a)} kernels there, {len(b)} here; identical bodies: {len(same)} ({sum(len(a[k]) for k in same)} "
-                  f"instructions), different: {len(diff)}, missing here: {len(gone)}, new here: {len([k for k in b if k not in a])}")
-            for k in diff + gone:
-                print("   ", k)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("other", help="the other source tree")
+    ap.add_argument("units", nargs="*", help="translation units (default: every unit of the build)")
+    ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 1))
+    a = ap.parse_args()
+    units = a.units or build.sources()
+    for unit in units:
+        build.source_flags(unit)  # (probe the optional flags once, before the threads)
+    with tempfile.TemporaryDirectory() as tmp, cf.ThreadPoolExecutor(max(1, min(16, a.jobs))) as ex:
+        def side(tree, tag):
+            def one(unit):
+                if not os.path.exists(os.path.join(tree, "geosss_amd", "csrc", unit)):
+                    return {}
+                return functions(tree, unit, tmp, f"{tag}_{unit}")
+            return one
+        there = list(ex.map(side(a.other, "other"), units))
+        here = list(ex.map(side(HERE, "this"), units))
+    union_there, union_here = {}, {}
+    for union, per_unit in ((union_there, there), (union_here, here)):
+        for fns in per_unit:
+            for k, body in fns.items():  # one name, several bodies (weak copies in several units): all of them
+                union.setdefault(k, set()).add(tuple(body))
+    for unit, x, y in zip(units, there, here):
+        report(unit, x, y)
+    bad = report("union of all units", union_there, union_here)
     sys.exit(1 if bad else 0)
 
 
