@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "gsss_batch.h"
+#include "gsss_batch_shared.h"
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
@@ -453,8 +453,12 @@ static int fast_refused(const gsss_target *t)
 // the pick goes to its family's launcher (tb: the target, or the launch's first member of a batch)
 static int fast_launch(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, bool replay, hipStream_t st)
 {
-    if (p.batch)
+    if (p.batch) {  // the plan gsss_batch_plan reports: workgroups shared among small targets, or one target per workgroup
+        BatchPlan bp;
+        if (rb.n_chains >= bi.m && batch_plan(tb.kind, tb.d, tb.k, rb.n_chains / bi.m, bi.m, bp) == GSSS_OK && bp.shared)
+            return tb.kind == GSSS_VMF_MIXTURE ? launch_shared_fast_vmf(p, bp, tb, rb, bi, st) : launch_shared_fast_bingham(p, bp, tb, rb, bi, st);
         return tb.kind == GSSS_VMF_MIXTURE ? launch_batch_fast_vmf(p, tb, rb, bi, st) : launch_batch_fast_bingham(p, tb, rb, bi, st);
+    }
     switch (tb.kind) {
     case GSSS_VMF_MIXTURE: return launch_fast_vmf(p, tb, rb, replay, st);
     case GSSS_BINGHAM: return launch_fast_bingham(p, tb, rb, replay, st);
@@ -1172,6 +1176,23 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
     }
     set_error("corrupt target");
     return GSSS_E_INVALID;
+}
+
+int gsss_batch_plan(int32_t kind, int32_t d, int32_t k, int32_t has_b, int64_t n_targets, int64_t m, int32_t *chains_per_workgroup,
+                    int32_t *targets_per_workgroup, int64_t *grid, double *lane_use)
+{
+    (void)has_b;  // (the rows of a Bingham member hold b either way; with the all-diagonal flag in k it names the shape in full)
+    BatchPlan bp;
+    if (batch_plan(kind, d, k, n_targets, m, bp) != GSSS_OK) {
+        set_error("no fast-mode batch kernel for kind %d, d=%d, k=%d with %lld targets of %lld chains (vMF mixtures: d = 3 .. 10 with "
+                  "K <= 16, d = 11 .. 16 with K <= 10; Bingham: d = 3 .. 16)", kind, d, k, (long long)n_targets, (long long)m);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (chains_per_workgroup) *chains_per_workgroup = bp.per_block;
+    if (targets_per_workgroup) *targets_per_workgroup = bp.targets;
+    if (grid) *grid = bp.grid;
+    if (lane_use) *lane_use = bp.lane_use;
+    return GSSS_OK;
 }
 
 int gsss_last_launch(int64_t *grid_out, int32_t *slice_steps_out, double *sliced_fraction_out)

@@ -80,6 +80,18 @@ struct FastVmf {
         mu = lds;
         logc = lds + KC * D;
     }
+    // the shared batch build (stage_shared): word i of a member's rows as stage() forms it, and a lane's view of rows staged so
+    __device__ static double staged(const double *blob, int k, int i)
+    {
+        if (i < KC * D) return i < k * D ? blob[i] : 0.0;
+        return i - KC * D < k ? fmax(blob[k * D + i - KC * D], kLogZero) : kLogZero;
+    }
+    __device__ __forceinline__ void attach(const double *rows, const TargetBlock &tb)
+    {
+        K = tb.k;
+        mu = rows;
+        logc = rows + KC * D;
+    }
     __device__ __forceinline__ double make(Coef &cf, const double (&x)[D], const double (&u)[D], double lvl,
                                            bool fresh) const
     {
@@ -174,6 +186,14 @@ struct FastBingham {
         for (int i = threadIdx.x; i < D * D + D; i += kBlock) lds[i] = tb.blob[i];
         A = lds;
         b = lds + D * D;
+        diagonal = (tb.k & 1) != 0;
+    }
+    // the shared batch build (stage_shared): as for FastVmf
+    __device__ static double staged(const double *blob, int /*k*/, int i) { return blob[i]; }
+    __device__ __forceinline__ void attach(const double *rows, const TargetBlock &tb)
+    {
+        A = rows;
+        b = rows + D * D;
         diagonal = (tb.k & 1) != 0;
     }
     __device__ __forceinline__ double make(Coef &cf, const double (&x)[D], const double (&u)[D], double /*lvl*/,
@@ -554,6 +574,36 @@ __host__ __device__ constexpr size_t fast_lds_doubles()
                                 : 0);
 }
 
+// The SHARED batch build (BatchShared, gsss_device.h), all of it before the first __syncthreads(): the draw tables lead the LDS
+// and the rows of the targets of this workgroup's run of consecutive chains follow, member i of the run at i shared_stride
+// doubles -- one strided copy out of the batch allocation, where the blobs lie at an equal stride.  The stride is the build's
+// rows padded to an ODD number of doubles: the lanes of a wavefront read the same row of up to ceil(64 / m) + 1 consecutive
+// members at once (ds_read_b64: 32 lanes a cycle over 32 eight-byte banks; ds_read2_b64: 16 lanes over 16), and consecutive
+// multiples of an odd number fall in different banks modulo 32 and modulo 16.  Returns the lane's chain (n: none) and attaches
+// tp to its target's rows: the lane's row base is all that stays live.
+template <class TP>
+__host__ __device__ inline int32_t shared_stride()
+{
+    return (int32_t)TP::lds_doubles() | 1;
+}
+template <class TP>
+__device__ __forceinline__ int32_t stage_shared(TP &tp, double *lds, const TargetBlock &tb, const BatchShared &sb, int32_t n)
+{
+    const int32_t rows = (int32_t)TP::lds_doubles(), stride = shared_stride<TP>();
+    const int32_t c0 = (int32_t)blockIdx.x * sb.per_block;
+    const int32_t c_last = (c0 + sb.per_block < n ? c0 + sb.per_block : n) - 1;
+    const int32_t t_first = c0 / sb.m, count = c_last / sb.m - t_first + 1;  // (<= the plan's targets: batch_targets_touched)
+    double *dst = lds + kTabLds;
+    for (int32_t i = threadIdx.x; i < count * rows; i += kBlock) {
+        const int32_t t = i / rows, r = i - t * rows;
+        dst[t * stride + r] = TP::staged(tb.blob + (int64_t)(t_first + t) * sb.stride, tb.k, r);
+    }
+    const int32_t c = c0 + (int32_t)threadIdx.x;
+    const bool mine = (int32_t)threadIdx.x < sb.per_block && c < n;
+    tp.attach(dst + (mine ? c / sb.m - t_first : 0) * stride, tb);
+    return mine ? c : n;
+}
+
 // NUMPY: the draws come from numpy's own PCG64 / ziggurat stream (rng_state, NumpyDraws) instead of the replay buffer, at
 // the replay path's consumption points -- the reference's own order, a uniform per try that is made and none for one that is
 // not.  A generator per chain: one chain per lane (nothing is parked), the ziggurat tables where the parked chains would be.
@@ -564,14 +614,20 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
 {
     static_assert(!NUMPY || REPLAY, "numpy's stream is a sequential source: it is read where the replay buffer is");
     static_assert(sizeof...(BB) == (BATCH ? 1 : 0) && !(BATCH && (REPLAY || STATS || NUMPY)),
-                  "the batch build takes one BatchBlock: library stream, no running statistics");
+                  "the batch build takes one BatchBlock (or BatchShared): library stream, no running statistics");
     using V = LaneVec<D>;
     using Chain = FastChain<D, TP>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     TP tp;
-    if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
-    tp.stage(lds, tb);
-    const fm::Tables tab = stage_tables(lds + TP::lds_doubles());
+    constexpr bool kShared = kIsBatchShared<BB...>;  // (BatchShared in BatchBlock's place: stage_shared above)
+    [[maybe_unused]] int32_t shared_id = 0;
+    if constexpr (kShared) {
+        shared_id = stage_shared(tp, lds, tb, first_of(batch...), (int32_t)a.n_chains);
+    } else {
+        if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
+        tp.stage(lds, tb);
+    }
+    const fm::Tables tab = stage_tables(kShared ? lds : lds + TP::lds_doubles());
     // word w of this lane's parked chain lives at park[w * kBlock]: conflict-free across lanes
     unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + TP::lds_doubles() + kTabLds) + threadIdx.x;
     NumpyDraws<V> nd;
@@ -591,7 +647,9 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
     const bool spread = a.spread != 0;
     int32_t id0 = spread ? ((threadIdx.x % 64 == 0) ? (int32_t)blockIdx.x * (kBlock / 64) + (int32_t)threadIdx.x / 64 : n)
                          : (int32_t)blockIdx.x * kPerBlock + (int32_t)threadIdx.x;
-    if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
+    if constexpr (kShared) {  // lane threadIdx.x of the workgroup's run of consecutive chains, or none (n)
+        id0 = shared_id;
+    } else if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
         const BatchBlock &bb = first_of(batch...);
         const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
         const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;

@@ -273,6 +273,97 @@ inline int fast_select(const FastAsk &a, FastPick &p)
     return GSSS_E_UNSUPPORTED;
 }
 
+// ------------------------------------------------------------------------------------------
+// The launch plan of a fast-mode batch: what gsss_run launches and gsss_batch_plan reports.  A pure function of the members'
+// shape (kind, d, K) and of m, the chains per target -- not of the variant a launch asks for (screened or all-double, diagonal
+// or dense Bingham), so that one answer holds for every launch of the batch: the LDS is budgeted for the widest rows any batch
+// kernel of the shape stages.
+//   m a multiple of the workgroup's 256 chains: today's launch (gsss_batch.h) -- one target per workgroup, targets x m / 256
+//   workgroups, every lane busy.
+//   otherwise the SHARED builds (gsss_batch_shared.h): a workgroup takes per_block consecutive chains of the launch and stages
+//   every target they touch.  per_block is the largest count <= 256 whose runs touch no more targets than the LDS SHARE holds:
+//   the CU's 160 KB (128 allocation granules of 1280 B) divided among as many workgroups as the registers of the shape's batch
+//   builds let a CU hold (batch_resident), so that staging more targets never costs a resident workgroup.
+// ------------------------------------------------------------------------------------------
+constexpr int kBatchBlock = 256;                  // = kBlock
+constexpr int kBatchTabDoubles = 2 * 64 + 2;      // = kTabLds: the draw tables every lane kernel stages
+constexpr long kBatchLdsBytes = 160 * 1024;       // = kMaxLdsBytes
+constexpr long kBatchLdsGranule = 1280;           // LDS is allocated in granules of 320 dwords on gfx950
+
+struct BatchPlan {
+    bool shared;     // the shared builds; else the builds of gsss_batch.h
+    int per_block;   // chains a workgroup takes
+    int targets;     // the most targets a workgroup stages
+    long long grid;  // workgroups: ceil(n_targets m / per_block)
+    double lane_use; // chains / (grid x per_block)
+    int stride;      // (shared) doubles a target is budgeted in LDS: the widest rows of the shape, padded to an odd count
+};
+
+namespace fast_select_detail {
+
+// the widest rows (doubles) a batch kernel of the shape stages per target: vMF mixtures K_C (d + 1) in the larger of the screened
+// and the all-double bucket; Bingham A and b (the diagonal screen target stages d of them)
+inline int batch_rows(int kind, int d, int k)
+{
+    if (kind == GSSS_BINGHAM) return d * d + d;
+    const bool wide = d >= 11;
+    const int ks = wide ? bucket(k, kWideBuckets) : bucket(k, kScreenBuckets);
+    const int kd = wide ? bucket(k, kBatchWideDoubleBuckets) : bucket(k, kDoubleBuckets);
+    return (ks > kd ? ks : kd) * (d + 1);
+}
+
+// Workgroups of 256 lanes a CU holds of the batch builds of the shape -- wavefronts per SIMD of their code objects, the most
+// over the shape's variants (a larger number only makes the share smaller).  tests/test_target_batch_plan.py holds the
+// code objects of the shared builds to it.  Read off the builds of gsss_batch.h: on S^2 five (88 .. 115 registers) but for
+// mixtures of K >= 5, everywhere else four (Bingham d = 4 .. 8 and 11 .. 13, mixtures in the buckets 3 and 4) or fewer; mixtures
+// of K >= 5 three (135 .. 168 registers screened, two for the all-double buckets 10 and 16).
+inline int batch_resident(int kind, int d, int k)
+{
+    if (kind == GSSS_VMF_MIXTURE && k >= 5) return 3;
+    return d == 3 ? 5 : 4;
+}
+
+// the most targets a run of c consecutive chains touches when runs start at multiples of c and targets at multiples of m: the
+// worst start lies m - gcd(c, m) chains into a target
+inline long long batch_targets_touched(long long c, long long m)
+{
+    long long g = c, r = m;
+    while (r) {
+        const long long t = g % r;
+        g = r;
+        r = t;
+    }
+    return (m - g + c - 1) / m + 1;
+}
+
+}  // namespace fast_select_detail
+
+// GSSS_OK and the plan of a batch of n_targets members with m chains each, or GSSS_E_UNSUPPORTED: no fast batch kernel
+inline int batch_plan(int kind, int d, int k, long long n_targets, long long m, BatchPlan &bp)
+{
+    using namespace fast_select_detail;
+    FastAsk a{};
+    a.kind = kind, a.d = d, a.k = kind == GSSS_BINGHAM ? 0 : k, a.screen = 1, a.batch = true;
+    FastPick p;
+    if ((kind != GSSS_VMF_MIXTURE && kind != GSSS_BINGHAM) || n_targets < 1 || m < 1 || fast_select(a, p) != GSSS_OK) return GSSS_E_UNSUPPORTED;
+    const long long n = n_targets * m;
+    bp = BatchPlan{};
+    bp.per_block = kBatchBlock;
+    bp.targets = 1;
+    bp.stride = batch_rows(kind, d, k) | 1;
+    if (m % kBatchBlock != 0) {
+        const long share = (kBatchLdsBytes / kBatchLdsGranule / batch_resident(kind, d, k)) * kBatchLdsGranule;
+        const long long fit = (share / 8 - kBatchTabDoubles) / bp.stride;  // >= 1: the largest rows are 272 doubles
+        bp.shared = true;
+        while (batch_targets_touched(bp.per_block, m) > fit) --bp.per_block;  // (one chain touches one target)
+        const long long touched = batch_targets_touched(bp.per_block, m);
+        bp.targets = (int)(touched < n_targets ? touched : n_targets);
+    }
+    bp.grid = (n + bp.per_block - 1) / bp.per_block;
+    bp.lane_use = (double)n / ((double)bp.grid * bp.per_block);
+    return GSSS_OK;
+}
+
 // the instantiation a pick stands for, e.g. "screened_kernel<3, ScreenVmf<3, 3>>" (", batch" appended for the batch build)
 inline void fast_name(const FastPick &p, char *buf, size_t n)
 {

@@ -85,6 +85,7 @@ struct ScreenVmf : FastVmf<D, KC> {
     // when 24 lanes want to is worth 9 % (K = 10, kappa = 500: 56.6 -> 51.7 ms per 10^9 chain-steps; 12: 52.5, 32: 59.2, 44: 71.7);
     // with the cheap swaps of K <= 5 and of the Bingham target waiting costs more than it saves (27.7 -> 28.3 / 28.6 ms at 12 / 24).
     static constexpr int kTradeMin = KC >= 6 ? 24 : 1;
+    static constexpr int kSharedMinWaves = kMinWaves;  // the shared batch build (BatchShared)
     static constexpr bool kCompact = false;
     // The one-chain-per-lane BUILD (screened_kernel<.., STAGE>: no code for a parked chain; do_screened_run) at any ensemble size
     // where it was measured ahead at 10^6 chains (profiles/r04_vmf_pure_one.log): bucket 10 at every
@@ -240,6 +241,7 @@ struct ScreenBingham : FastBingham<D> {
     using Coef = typename Base::Coef;
     static constexpr int kCoef32Floats = 6;
     static constexpr int kParkSkip = 0, kMinWaves = D > 10 ? 2 : 1, kTradeMin = 1;
+    static constexpr int kSharedMinWaves = kMinWaves;  // the shared batch build (BatchShared)
     static constexpr bool kCompact = false, kRegenThr = false, kStageRows = true;
     static constexpr bool kPreferOne = D != 6;  // the one-chain-per-lane build at any ensemble size (do_screened_run)
     static constexpr bool kHoldRows = true;
@@ -315,6 +317,7 @@ struct ScreenBinghamDiag {
     static constexpr bool kLinear = false;
     static constexpr int kCoef32Floats = 4;  // q0 = -log U, q1 = qxu, q2 = (quu - qxx) - log U | margin
     static constexpr int kParkSkip = 0, kMinWaves = D >= 14 ? 2 : (D >= 9 ? 3 : 1), kTradeMin = 1;  // (d >= 14 spills at three)
+    static constexpr int kSharedMinWaves = D == 13 ? 2 : kMinWaves;  // the shared batch build: a lane's row base on top (d = 13 spills 28 B at three)
     static constexpr bool kCompact = true, kRegenThr = true, kStageRows = true;
     static constexpr bool kPreferOne = D >= 5;  // the one-chain-per-lane build at any ensemble size (do_screened_run)
     static constexpr bool kHoldRows = true;
@@ -329,6 +332,9 @@ struct ScreenBinghamDiag {
         for (int i = threadIdx.x; i < D; i += kBlock) lds[i] = tb.blob[(size_t)i * D + i];
         a = lds;
     }
+    // the shared batch build (stage_shared, gsss_fast.h): as for FastVmf
+    __device__ static double staged(const double *blob, int /*k*/, int i) { return blob[(size_t)i * D + i]; }
+    __device__ __forceinline__ void attach(const double *rows, const TargetBlock &) { a = rows; }
     __device__ __forceinline__ double make(Coef &cf, const double (&x)[D], const double (&u)[D]) const
     {
         double qxx = 0.0, qxu = 0.0, quu = 0.0;
@@ -796,6 +802,16 @@ __device__ __forceinline__ void lds_trade(float &a, float &b, unsigned long long
     b = __uint_as_float((uint32_t)(o >> 32));
 }
 
+// wavefronts per SIMD a plain launch is built for; the shared batch build (BatchShared) of the three batch targets: their own figure
+template <class TP, bool SHARED>
+__host__ __device__ constexpr int screen_min_waves()
+{
+    if constexpr (SHARED)
+        return TP::kSharedMinWaves;
+    else
+        return TP::kMinWaves;
+}
+
 // (measured: asking for two wavefronts per SIMD at d = 10 makes the curve kernel spill 73 registers: 45 -> 64 ms)
 // NUMPY (round 4): the draws come from numpy's own PCG64 / ziggurat stream (RunBlock::rng_state, NumpyDraws) at the replay
 // path's consumption points -- the reference's order: d normals, the threshold uniform, theta_0, then a uniform per try that
@@ -807,19 +823,25 @@ __device__ __forceinline__ void lds_trade(float &a, float &b, unsigned long long
 // per lane (launched with one_per_lane and without a slice plan), no code for a parked chain.  All of it happens before the first
 // step: a lane past its target's block takes the chain id n, as the empty second slot of a one-per-lane launch does.
 template <int D, class TP, bool REPLAY, bool STATS = false, bool STAGE = false, bool NUMPY = false, bool BATCH = false, class... BB>
-__global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (NUMPY ? TP::kNumpyWaves : TP::kMinWaves))
+__global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (NUMPY ? TP::kNumpyWaves : screen_min_waves<TP, kIsBatchShared<BB...>>()))
     screened_kernel(TargetBlock tb, RunBlock a, BB... batch)  // (NUMPY: the generator's state and the ziggurat's temporaries on top of the plain kernel's registers)
 {
     static_assert(!NUMPY || (REPLAY && !STAGE), "numpy's stream is a sequential source: it is read where the replay buffer is");
     static_assert(sizeof...(BB) == (BATCH ? 1 : 0) && !(BATCH && (REPLAY || STATS || STAGE || NUMPY)),
-                  "the batch build takes one BatchBlock: library stream, no running statistics");
+                  "the batch build takes one BatchBlock (or BatchShared): library stream, no running statistics");
     using V = LaneVec<D>;
     using Chain = ScreenChain<D, TP>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     TP tp;
-    if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
-    tp.stage(lds, tb);
-    const fm::Tables tab = stage_tables(lds + TP::lds_doubles());
+    constexpr bool kShared = kIsBatchShared<BB...>;  // (BatchShared in BatchBlock's place: stage_shared, gsss_fast.h)
+    [[maybe_unused]] int32_t shared_id = 0;
+    if constexpr (kShared) {
+        shared_id = stage_shared(tp, lds, tb, first_of(batch...), (int32_t)a.n_chains);
+    } else {
+        if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
+        tp.stage(lds, tb);
+    }
+    const fm::Tables tab = stage_tables(kShared ? lds : lds + TP::lds_doubles());
     unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + TP::lds_doubles() + kTabLds) + threadIdx.x;
     NumpyDraws<V> nd;
     if constexpr (NUMPY) nd.stage(lds + TP::lds_doubles() + kTabLds);
@@ -859,7 +881,9 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     constexpr int kPerBlock = kPark ? 2 * kBlock : kBlock;
     // (one_per_lane: kBlock chains per workgroup, the lane's second slot stays empty -- a chain id past the ensemble)
     int32_t id0 = (int32_t)chunk * (a.one_per_lane ? kBlock : kPerBlock) + (int32_t)threadIdx.x;
-    if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
+    if constexpr (kShared) {  // lane threadIdx.x of the workgroup's run of consecutive chains, or none (n)
+        id0 = shared_id;
+    } else if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
         const BatchBlock &bb = first_of(batch...);
         const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
         const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;

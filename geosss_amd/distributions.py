@@ -513,6 +513,18 @@ class TargetBatch(Distribution):
             cache[(dev, int(chains_per_target))] = (key, _DeviceTarget(arrays, kind, d, k, kappa, dev, extra))
         return cache[(dev, int(chains_per_target))][1]
 
+    def launch_plan(self, chains_per_target):
+        """How a fast-mode launch of the whole batch with `chains_per_target` chains each is laid out on the chip
+        (gsss_batch_plan; no device needed): the chains a workgroup takes, the most targets it stages, the grid, and the share of
+        the launched lanes that carry a chain.  Small m is packed: a workgroup takes a run of consecutive chains and serves every
+        target the run touches.  ValueError where the batch has no fast kernel."""
+        kind, d, k = self._pack()[:3]
+        has_b = int(kind == _lib.BINGHAM and self._member_packs()[0][4][0] is not None)
+        cpw, tpw, grid, use = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double()
+        _lib.check(_lib.load().gsss_batch_plan(kind, d, k, has_b, len(self.pdfs), int(chains_per_target), C.byref(cpw), C.byref(tpw),
+                                               C.byref(grid), C.byref(use)))
+        return {"chains_per_workgroup": cpw.value, "targets_per_workgroup": tpw.value, "grid": grid.value, "lane_use": use.value}
+
     def _per_member(self, x, what):
         M, d = len(self.pdfs), self.d
         if isinstance(x, torch.Tensor):

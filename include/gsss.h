@@ -300,6 +300,17 @@ int gsss_run(const gsss_target *t, const gsss_run_args *args, void *stream);
  * replaces. */
 int gsss_last_launch(int64_t *grid_out, int32_t *slice_steps_out, double *sliced_fraction_out);
 
+/* The fast-mode launch plan of a batch of n_targets members (kind, d, k, has_b) with m chains each: chains a workgroup takes, the
+ * most targets it stages, the grid, and lanes that carry a chain / lanes launched (chains / (grid x chains a workgroup takes)).
+ * k: the components of a vMF mixture; ignored for GSSS_BINGHAM, like has_b -- one plan holds for every launch of a shape, screened
+ * or all-double, diagonal or dense (its LDS is budgeted for the widest rows).  m a multiple of 256: one target per workgroup, 256
+ * chains; otherwise a workgroup takes a run of consecutive chains and stages every target the run touches, as many as the LDS
+ * holds without costing the kernel a resident workgroup.  gsss_run launches what this reports.  A pure host function: no device
+ * is needed.  Any output pointer may be NULL.  GSSS_E_UNSUPPORTED where the batch has no fast kernel.  There is nothing in the
+ * reference this replaces. */
+int gsss_batch_plan(int32_t kind, int32_t d, int32_t k, int32_t has_b, int64_t n_targets, int64_t m,
+                    int32_t *chains_per_workgroup, int32_t *targets_per_workgroup, int64_t *grid, double *lane_use);
+
 /* Number of rows of gsss_run_args.stats_dev for dimension d, K modes, L lags and the GSSS_STATS_* flags (< 0: bad argument). */
 int64_t gsss_stats_rows(int32_t d, int32_t n_modes, int32_t n_lags, int32_t flags);
 

@@ -5,7 +5,10 @@ M in {1, 64, 1024, 4096} targets x m in {256, 1024} chains each, 1000 steps per 
 process, timed with events on the launch stream after a warm-up launch.  The batch side is timed over 20 launches; a repetition
 of the loop side is M launches, repeated until at least 20 launches are timed (LOOP_REPS overrides).  Last, what the batch
 indexing itself costs: M = 1, m = 10^6 against the plain one-chain-per-lane launch of the same target.
-    MS=1,64 SIZES=256 python tools/bench_target_batch.py      # a subset"""
+    MS=1,64 SIZES=256 python tools/bench_target_batch.py      # a subset
+SMALL=16,64,100,256,300,1024: instead, the shape the type is for -- many small targets, M m ~ 10^6 chains (M = 10^6 // m) -- the
+batch launch alone (a loop of 10^4 .. 10^5 samplers is not a baseline anybody runs), with the launch plan where the library
+reports one (TargetBatch.launch_plan): the rows of DESIGN.md section 5.6c, taken on the parent and on this tree on one box."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -39,7 +42,25 @@ def timed(fn, reps):
     return t0.elapsed_time(t1) * 1e-3 / reps
 
 
+def small_targets(sizes):
+    cls = gs.ShrinkageSphericalSliceSampler
+    for name in ("bingham_d5", "vmfmix_readme"):
+        for m in sizes:
+            M = 1_000_000 // m
+            batch = gs.TargetBatch(members(name, M))
+            d = batch.d
+            x0 = gs.sample_sphere_device(d - 1, M * m, seed=1).T.contiguous()
+            sb = cls(batch, x0, 3521, mode="fast")
+            out = torch.empty((STEPS // THIN, d, M * m), dtype=torch.float64, device=x0.device)
+            t = timed(lambda: sb.advance(STEPS, thin=THIN, out=out), REPS)
+            plan = batch.launch_plan(m) if hasattr(batch, "launch_plan") else {}
+            print(f"{name:14s} M={M:6d} m={m:5d}: batch {M * m * STEPS / t:.3e} chain-steps/s ({t * 1e3:9.3f} ms a launch)   {plan}", flush=True)
+            del sb, out, x0, batch
+
+
 def main():
+    if os.environ.get("SMALL"):
+        return small_targets([int(v) for v in os.environ["SMALL"].split(",")])
     Ms = [int(v) for v in os.environ.get("MS", "1,64,1024,4096").split(",")]
     sizes = [int(v) for v in os.environ.get("SIZES", "256,1024").split(",")]
     cls = gs.ShrinkageSphericalSliceSampler
