@@ -1,8 +1,8 @@
-// shared batch builds of the lane kernels for Bingham targets at d = 7 .. 10 (see gsss_batch_shared.h)
-#include "gsss_batch_shared.h"
+// shared batch builds (BatchShared) of the lane kernels for Bingham / Fisher-Bingham targets at d = 7, 8, 9, 10 (see gsss_batch.h)
+#include "gsss_batch.h"
 namespace gsss {
-template int shared_lane_bingham<7>(GSSS_SHARED_ARGS);
-template int shared_lane_bingham<8>(GSSS_SHARED_ARGS);
-template int shared_lane_bingham<9>(GSSS_SHARED_ARGS);
-template int shared_lane_bingham<10>(GSSS_SHARED_ARGS);
+template int batch_lane_bingham<7, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_bingham<8, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_bingham<9, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_bingham<10, BatchShared>(GSSS_BATCH_ARGS);
 }

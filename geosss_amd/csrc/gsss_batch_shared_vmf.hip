@@ -1,26 +1,7 @@
-// GSSS_MODE_FAST launcher for a batch of vMF mixtures whose plan shares workgroups among targets, and the shared batch builds of
-// the lane kernels at d = 3 .. 5 (gsss_batch_shared.h); the other dimensions are built in gsss_batch_shared_vmf_{b,c,wide_a,wide_b}.hip.
-#include "gsss_batch_shared.h"
-
+// shared batch builds (BatchShared) of the lane kernels for vMF mixtures at d = 3 .. 5 (see gsss_batch.h)
+#include "gsss_batch.h"
 namespace gsss {
-
-template int shared_lane_vmf<3>(GSSS_SHARED_ARGS);
-template int shared_lane_vmf<4>(GSSS_SHARED_ARGS);
-template int shared_lane_vmf<5>(GSSS_SHARED_ARGS);
-
-int launch_shared_fast_vmf(const FastPick &p, const BatchPlan &bp, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
-{
-    switch (p.d) {
-#define GSSS_CASE(D) \
-    case D: return shared_lane_vmf<D>(p, bp, tb, rb, bi, st);
-        GSSS_BATCH_LANE_DIMS(GSSS_CASE)
-#undef GSSS_CASE
-#define GSSS_CASE(D) \
-    case D: return shared_lane_vmf_wide<D>(p, bp, tb, rb, bi, st);
-        GSSS_BATCH_WIDE_DIMS(GSSS_CASE)
-#undef GSSS_CASE
-    }
-    return pick_error(p);
+template int batch_lane_vmf<3, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_vmf<4, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_vmf<5, BatchShared>(GSSS_BATCH_ARGS);
 }
-
-}  // namespace gsss

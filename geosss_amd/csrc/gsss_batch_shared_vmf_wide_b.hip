@@ -1,7 +1,7 @@
-// shared batch builds of the lane kernels for vMF mixtures at d = 14, 15, 16 (see gsss_batch_shared.h)
-#include "gsss_batch_shared.h"
+// shared batch builds (BatchShared) of the lane kernels for vMF mixtures at d = 14, 15, 16 (see gsss_batch.h)
+#include "gsss_batch.h"
 namespace gsss {
-template int shared_lane_vmf_wide<14>(GSSS_SHARED_ARGS);
-template int shared_lane_vmf_wide<15>(GSSS_SHARED_ARGS);
-template int shared_lane_vmf_wide<16>(GSSS_SHARED_ARGS);
+template int batch_lane_vmf_wide<14, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_vmf_wide<15, BatchShared>(GSSS_BATCH_ARGS);
+template int batch_lane_vmf_wide<16, BatchShared>(GSSS_BATCH_ARGS);
 }

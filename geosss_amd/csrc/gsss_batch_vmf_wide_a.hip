@@ -1,7 +1,7 @@
-// batch builds of the screened lane kernels for vMF mixtures at d = 11, 12, 13 (see gsss_batch.h)
+// batch builds (BatchBlock) of the lane kernels for vMF mixtures at d = 11, 12, 13 (see gsss_batch.h)
 #include "gsss_batch.h"
 namespace gsss {
-template int batch_lane_vmf_wide<11>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t);
-template int batch_lane_vmf_wide<12>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t);
-template int batch_lane_vmf_wide<13>(const FastPick &, const TargetBlock &, const RunBlock &, const BatchInfo &, hipStream_t);
+template int batch_lane_vmf_wide<11, BatchBlock>(GSSS_BATCH_ARGS);
+template int batch_lane_vmf_wide<12, BatchBlock>(GSSS_BATCH_ARGS);
+template int batch_lane_vmf_wide<13, BatchBlock>(GSSS_BATCH_ARGS);
 }

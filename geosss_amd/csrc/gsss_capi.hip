@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "gsss_batch_shared.h"
+#include "gsss_batch.h"
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
@@ -455,9 +455,14 @@ static int fast_launch(const FastPick &p, const TargetBlock &tb, const RunBlock 
 {
     if (p.batch) {  // the plan gsss_batch_plan reports: workgroups shared among small targets, or one target per workgroup
         BatchPlan bp;
-        if (rb.n_chains >= bi.m && batch_plan(tb.kind, tb.d, tb.k, rb.n_chains / bi.m, bi.m, bp) == GSSS_OK && bp.shared)
-            return tb.kind == GSSS_VMF_MIXTURE ? launch_shared_fast_vmf(p, bp, tb, rb, bi, st) : launch_shared_fast_bingham(p, bp, tb, rb, bi, st);
-        return tb.kind == GSSS_VMF_MIXTURE ? launch_batch_fast_vmf(p, tb, rb, bi, st) : launch_batch_fast_bingham(p, tb, rb, bi, st);
+        if (batch_plan(tb.kind, tb.d, tb.k, rb.n_chains / bi.m, bi.m, bp) != GSSS_OK) {  // (it asks fast_select what the pick came from)
+            set_error("target batch: no launch plan for kind %d, d=%d, k=%d with %lld chains, %lld per target", tb.kind, tb.d, tb.k,
+                      (long long)rb.n_chains, (long long)bi.m);
+            return GSSS_E_UNSUPPORTED;
+        }
+        const bool vmf = tb.kind == GSSS_VMF_MIXTURE;
+        if (bp.shared) return vmf ? launch_batch_fast_vmf<BatchShared>(p, bp, tb, rb, bi, st) : launch_batch_fast_bingham<BatchShared>(p, bp, tb, rb, bi, st);
+        return vmf ? launch_batch_fast_vmf<BatchBlock>(p, bp, tb, rb, bi, st) : launch_batch_fast_bingham<BatchBlock>(p, bp, tb, rb, bi, st);
     }
     switch (tb.kind) {
     case GSSS_VMF_MIXTURE: return launch_fast_vmf(p, tb, rb, replay, st);

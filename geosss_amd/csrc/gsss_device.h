@@ -79,7 +79,7 @@ struct BatchBlock {
     int32_t m;       // chains per target
     int32_t chunks;  // workgroups per target: ceil(m / chains per workgroup)
 };
-// The SHARED batch build of the lane kernels (screened_kernel, fast_kernel; gsss_batch_shared.h): BATCH with this block in
+// The SHARED batch build of the lane kernels (screened_kernel, fast_kernel; gsss_batch.h): BATCH with this block in
 // BatchBlock's place -- the flag's third value is carried by the argument's type, so that the flag stays the bool it is in the
 // name of every other instantiation.  Workgroup b takes the consecutive chains [b per_block, (b + 1) per_block) of the launch,
 // whichever targets they belong to (chain c: target c / m), and stages the blobs of all of them, each at the build's own LDS

@@ -278,9 +278,9 @@ inline int fast_select(const FastAsk &a, FastPick &p)
 // shape (kind, d, K) and of m, the chains per target -- not of the variant a launch asks for (screened or all-double, diagonal
 // or dense Bingham), so that one answer holds for every launch of the batch: the LDS is budgeted for the widest rows any batch
 // kernel of the shape stages.
-//   m a multiple of the workgroup's 256 chains: today's launch (gsss_batch.h) -- one target per workgroup, targets x m / 256
+//   m a multiple of the workgroup's 256 chains: the BatchBlock builds (gsss_batch.h) -- one target per workgroup, targets x m / 256
 //   workgroups, every lane busy.
-//   otherwise the SHARED builds (gsss_batch_shared.h): a workgroup takes per_block consecutive chains of the launch and stages
+//   otherwise the SHARED builds (BatchShared): a workgroup takes per_block consecutive chains of the launch and stages
 //   every target they touch.  per_block is the largest count <= 256 whose runs touch no more targets than the LDS SHARE holds:
 //   the CU's 160 KB (128 allocation granules of 1280 B) divided among as many workgroups as the registers of the shape's batch
 //   builds let a CU hold (batch_resident), so that staging more targets never costs a resident workgroup.
@@ -291,7 +291,7 @@ constexpr long kBatchLdsBytes = 160 * 1024;       // = kMaxLdsBytes
 constexpr long kBatchLdsGranule = 1280;           // LDS is allocated in granules of 320 dwords on gfx950
 
 struct BatchPlan {
-    bool shared;     // the shared builds; else the builds of gsss_batch.h
+    bool shared;     // the BatchShared builds; else the BatchBlock ones (gsss_batch.h)
     int per_block;   // chains a workgroup takes
     int targets;     // the most targets a workgroup stages
     long long grid;  // workgroups: ceil(n_targets m / per_block)
@@ -314,7 +314,7 @@ inline int batch_rows(int kind, int d, int k)
 
 // Workgroups of 256 lanes a CU holds of the batch builds of the shape -- wavefronts per SIMD of their code objects, the most
 // over the shape's variants (a larger number only makes the share smaller).  tests/test_target_batch_plan.py holds the
-// code objects of the shared builds to it.  Read off the builds of gsss_batch.h: on S^2 five (88 .. 115 registers) but for
+// code objects of the shared builds to it.  Read off the BatchBlock builds: on S^2 five (88 .. 115 registers) but for
 // mixtures of K >= 5, everywhere else four (Bingham d = 4 .. 8 and 11 .. 13, mixtures in the buckets 3 and 4) or fewer; mixtures
 // of K >= 5 three (135 .. 168 registers screened, two for the all-double buckets 10 and 16).
 inline int batch_resident(int kind, int d, int k)
