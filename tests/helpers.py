@@ -27,6 +27,28 @@ def product_target(z, prefix="target_"):
     raise ValueError(kind)
 
 
+def mixture_target(z, prefix=""):
+    """The MixtureModel of a gmix_* fixture, rebuilt from its flat component list (tests/golden/make_golden_mixtures.py)."""
+    import geosss_amd as gs
+    comps = []
+    for i, kind in enumerate(z[prefix + "spec_kinds"]):
+        a = lambda name: z[f"{prefix}spec_{i}_{name}"]  # noqa: E731
+        kind = str(kind)
+        if kind == "vmf":
+            comps.append(gs.VonMisesFisher(a("mu")))
+        elif kind == "bingham":
+            comps.append(gs.Bingham(a("A")))
+        elif kind == "binghamfisher":
+            comps.append(gs.BinghamFisher(a("A"), a("b")))
+        elif kind == "uniform":
+            comps.append(gs.Uniform())
+        elif kind == "curve":
+            comps.append(gs.CurvedVonMisesFisher(gs.SlerpCurve(a("knots")), float(a("kappa"))))
+        else:
+            comps.append(gs.MixtureModel([gs.VonMisesFisher(m) for m in a("mus")], a("w")))
+    return gs.MixtureModel(comps, z[prefix + "spec_weights"])
+
+
 def variants_for(d, max_coop=2):
     """Default variant (0) plus up to `max_coop` cooperative layouts that cover d."""
     out = [0]
