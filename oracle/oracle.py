@@ -105,7 +105,7 @@ class Target:
         source, target = _f64(source), _f64(target)
         t = cls(CPD, 4, len(source))
         t.src, t.src_w, t.tgt, t.tgt_w = source, _f64(source_w), target, _f64(target_w)
-        log_volume = float(np.sum(np.log(np.ptp(target, 0))))                   # registration.py:207-213
+        log_volume = float(np.sum(np.log(np.ptp(target, 0)))) if outlier else 0.0   # registration.py:207-213 (the outlier box)
         t.c = _Target(CPD, 4, len(source), None, None, None, None, None, None, 0.0, _p(t.src), _p(t.src_w), _p(t.tgt),
                       _p(t.tgt_w), len(target), target.shape[1], int(k_nn), int(bool(outlier)), float(sigma), float(beta),
                       float(omega), log_volume)

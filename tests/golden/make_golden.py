@@ -547,6 +547,47 @@ def make_cpd():
         save(f"mh_hmc_{name}.npz", x0=x0, grad_X=GX, grad=grad, **flat_params(target_params(pdf)), **hm)
 
 
+def make_cpd_weighted():
+    """Registration with non-uniform weights on both clouds -- what the trajectory fixtures above never have: the reference's
+    log_prob and gradient on seeded standard-normal clouds (40 source points with weights log-uniform over e^-3 .. e^3, 30 target
+    points with weights uniform(0.5, 2)), k = 1, 8, 9, 24, a 3-D target and a projected one, GaussianMixtureModel and
+    CoherentPointDrift(omega = 0.2), sigma = 0.5, at 16 unit quaternions each.
+
+    k = 1: scipy's KDTree.query(k=1) drops the neighbour axis, and the reference's logsumexp(axis=1) / hstack then raise.  For
+    that k alone the classes below hand the reference's own `_query` the list [1] as its k, which keeps the (Lt, 1) shape."""
+    from geosss.pointcloud import PointCloud, RotationProjection
+    from geosss.registration import CoherentPointDrift, GaussianMixtureModel
+
+    def keep_axis(cls):
+        def _query(self, *args):
+            if self.k != 1:
+                return cls._query(self, *args)
+            self.k = [1]
+            try:
+                return cls._query(self, *args)
+            finally:
+                self.k = 1
+        return type(cls.__name__, (cls,), {"_query": _query})
+
+    GaussianMixtureModel, CoherentPointDrift = keep_axis(GaussianMixtureModel), keep_axis(CoherentPointDrift)
+    rng = np.random.default_rng(20261017)
+    a = {"sigma": np.float64(0.5), "beta": np.float64(1.0), "omega": np.float64(0.2), "ks": np.array([1, 8, 9, 24])}
+    for tag, dt, cloud in (("3d", 3, PointCloud), ("2d", 2, RotationProjection)):
+        src, tgt = rng.standard_normal((40, 3)), rng.standard_normal((30, dt))
+        sw, tw = np.exp(rng.uniform(-3.0, 3.0, 40)), rng.uniform(0.5, 2.0, 30)
+        Q = rsphere.radial_projection(rng.standard_normal((16, 4)))
+        a[f"{tag}_source"], a[f"{tag}_source_w"], a[f"{tag}_target"], a[f"{tag}_target_w"], a[f"{tag}_q"] = src, sw, tgt, tw, Q
+        for k in a["ks"]:
+            for model in ("gmm", "cpd"):
+                if model == "gmm":
+                    pdf = GaussianMixtureModel(PointCloud(tgt, tw), cloud(src, sw), sigma=0.5, k=int(k), beta=1.0)
+                else:
+                    pdf = CoherentPointDrift(PointCloud(tgt, tw), cloud(src, sw), sigma=0.5, k=int(k), beta=1.0, omega=0.2)
+                a[f"{tag}_k{k}_{model}_logp"] = np.array([float(pdf.log_prob(q)) for q in Q])
+                a[f"{tag}_k{k}_{model}_grad"] = np.array([pdf.gradient(q) for q in Q])
+    save("cpd_weighted_kat.npz", **a)
+
+
 def make_helpers():
     """Known answers of the reference's helper functions either side of the sampler: geosss/sphere.py coordinate maps,
     great-circle interpolation / rotation, sample_subsphere / sample_marginal, the host-side densities of
@@ -654,13 +695,15 @@ def make_helpers():
 
 
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["traj", "logprob", "geometry", "stats", "timing", "diagnostics", "mh", "mhk", "cpd", "helpers"]
+    what = sys.argv[1:] or ["traj", "logprob", "geometry", "stats", "timing", "diagnostics", "mh", "mhk", "cpd", "cpd_weighted", "helpers"]
     if "helpers" in what:
         make_helpers()
     if "mhk" in what:
         make_mh_kernels()
     if "cpd" in what:
         make_cpd()
+    if "cpd_weighted" in what:
+        make_cpd_weighted()
     if "mh" in what:
         make_mh()
     if "timing" in what:

@@ -482,6 +482,68 @@ def test_edge_targets_match_oracle(gs, oracle_mod, case):
     assert np.max(np.abs(kept - want["samples"])) < 1e-10, info
 
 
+def _registration_target(gs, oracle, rng):
+    """A registration target drawn over the whole range the kernel is built for: 1 .. 200 source and 1 .. 60 target points (the
+    small sizes and the list sizes 8, 9, 24, 25 drawn more often than one in 200), k = 1 .. min(24, source points), a 3-D or a
+    projected target, weights on both clouds or on neither, CoherentPointDrift with omega 0 or 0.2 or the mixture without the
+    outlier column, sigma log-uniform over 0.05 .. 2.  (A single target point has a box of no volume, and CoherentPointDrift's
+    outlier column is +inf in the reference too: it gets the mixture.)"""
+    ns = int(rng.choice([1, 2, 8, 9, 24, 25])) if rng.random() < 0.3 else int(rng.integers(1, 201))
+    nt = int(rng.choice([1, 2, 3])) if rng.random() < 0.2 else int(rng.integers(1, 61))
+    k = int(rng.integers(1, min(24, ns) + 1))
+    dt = int(rng.choice([2, 3]))
+    weighted = bool(rng.random() < 0.6)
+    omega = float(rng.choice([0.0, 0.2]))
+    cpd = nt > 1 and rng.random() < 0.75
+    sigma = float(np.exp(rng.uniform(np.log(0.05), np.log(2.0))))
+    src, tgt = rng.standard_normal((ns, 3)), rng.standard_normal((nt, dt))
+    sw = np.exp(rng.uniform(-3.0, 3.0, ns)) if weighted else np.ones(ns)
+    tw = rng.uniform(0.5, 2.0, nt) if weighted else np.ones(nt)
+    source = (gs.RotationProjection if dt == 2 else gs.PointCloud)(src, sw)
+    if cpd:
+        pdf = gs.CoherentPointDrift(gs.PointCloud(tgt, tw), source, sigma, k, omega=omega)
+    else:
+        pdf = gs.GaussianMixtureModel(gs.PointCloud(tgt, tw), source, sigma, k)
+    what = f"{'cpd' if cpd else 'gmm'} ns={ns} nt={nt} k={k} {dt}-D {'weighted' if weighted else 'uniform'} omega={omega if cpd else 0.0} sigma={sigma:.3f}"
+    return pdf, oracle.Target.cpd(src, sw, tgt, tw, sigma, k, 1.0, omega if cpd else 0.0, cpd), what, sigma
+
+
+@pytest.mark.parametrize("case", range(24 * SCALE))
+def test_registration_targets_match_oracle(gs, oracle_mod, case):
+    """The edge-target comparison above on registration targets (a draw of their own: the cases above keep theirs): either slice
+    sampler against the CPU oracle on the same Philox stream, states at 1e-10, tries exact, no error flag; log_prob and gradient
+    at the starting poses at 1e-10 of max(1, |value|) as well."""
+    oracle = oracle_mod
+    rng = np.random.default_rng(8000 + case)
+    pdf, tgt, what, sigma = _registration_target(gs, oracle, rng)
+    n, n_steps = 200, 20
+    sampler = "reject" if rng.random() < 0.3 and sigma > 0.7 else "shrink"   # (a sharp target rejects for thousands of tries)
+    if sampler == "reject":
+        n_steps = 5
+    cls = gs.RejectionSphericalSliceSampler if sampler == "reject" else gs.ShrinkageSphericalSliceSampler
+    kind = oracle.REJECT if sampler == "reject" else oracle.SHRINK
+    x0 = oracle.sample_sphere(int(rng.integers(1 << 20)), n, 4)
+    seed = int(rng.integers(1 << 30))
+    info = (what, sampler)
+    lp, want_lp = pdf.log_prob(x0), tgt.log_prob(x0)
+    assert np.max(np.abs(lp - want_lp) / np.maximum(1.0, np.abs(want_lp))) < 1e-10, info
+    gr, want_gr = pdf.gradient(x0[:40]), np.array([oracle.gradient(tgt, x) for x in x0[:40]])
+    assert np.max(np.abs(gr - want_gr) / np.maximum(1.0, np.max(np.abs(want_gr), axis=1, keepdims=True))) < 1e-10, info
+    want = oracle.run(tgt, x0, n_steps, seed=seed, sampler=kind, n_threads=16)
+    s = cls(pdf, x0, seed=seed)
+    assert s.mode == "exact", info
+    kept = s.advance(n_steps, thin=1).permute(2, 0, 1).cpu().numpy()
+    assert np.all(want["err"] == 0) and np.all(s.errors == 0), info
+    assert np.array_equal(s.n_tries_per_chain, want["n_tries"]), info
+    assert np.max(np.abs(kept - want["samples"])) < 1e-10, info
+    # the target's device copy lives on the distribution object: drop it here, not whenever the collector next runs
+    import gc
+    import torch
+    del s, pdf
+    gc.collect()
+    torch.cuda.synchronize()
+
+
 def test_concurrent_host_threads_and_streams(gs):
     """Four host threads, each with its own HIP stream and samplers of its own (lane kernel with a sliced last round, group kernel
     with every chunk sliced, exact kernel, RWMH), launching at the same time: the library's host side keeps per-thread error text

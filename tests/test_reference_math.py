@@ -1,7 +1,8 @@
 """The extended-precision reference (tests/reference_math.py) against what is known independently of it -- every log_prob and
-gradient the reference project recorded -- then the CPU oracle against it over the dimension sweep of the layout tests, and
-its own longdouble arithmetic against mpmath at 50 digits.  CPU only.  The last two tests evaluate, with the reference alone,
-the conditions the GPU modules assert of their cases: the try margins of the reference chains and the curve's near-ties."""
+gradient the reference project recorded, the registration targets' included -- then the CPU oracle against it over the dimension
+sweep of the layout tests and over the registration cases (tests/registration_cases.py), and its own longdouble arithmetic
+against mpmath at 50 digits.  CPU only.  The last tests evaluate, with the reference alone, the conditions the GPU modules assert
+of their cases: the try margins of the reference chains and the curve's near-ties."""
 import os
 
 import mpmath
@@ -10,6 +11,7 @@ import pytest
 
 import layout_cases as lc
 import reference_math as rm
+import registration_cases as rc
 from conftest import GOLDEN, golden
 from helpers import mixture_target, product_target
 from layout_cases import gradient_error, near_tie_rows, rel
@@ -17,9 +19,9 @@ from layout_cases import gradient_error, near_tie_rows, rel
 KAT_TOL = 1e-12  # relative-or-absolute: the bar the oracle is held to on the same answers (test_oracle_golden.py, test_oracle_mh.py)
 LOGPROB_KAT = sorted({k.split("__")[0] for k in golden("logprob_kat.npz").files})
 GMIX_KAT = sorted({k.split("__")[0] for k in golden("gmix_kat.npz").files})
-# the registration targets (CoherentPointDrift, GaussianMixtureModel) are not restated by the reference module
-MH_GRAD = sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("mh_") and f.endswith(".npz") and "_cpd_" not in f
-                 and "_gmm_protein" not in f and "grad_X" in golden(f).files and len(golden(f)["grad_X"]) > 0)
+MH_GRAD = sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("mh_") and f.endswith(".npz") and "grad_X" in golden(f).files
+                 and len(golden(f)["grad_X"]) > 0)
+REGISTRATION_KAT = ["cpd_protein", "gmm_protein_k10", "cpd_cube_3d2d"]
 
 
 def test_longdouble_is_extended():
@@ -52,7 +54,117 @@ def test_reproduces_recorded_mixture_logprob_and_gradient(name):
 def test_reproduces_recorded_gradient(name):
     z = golden(name + ".npz")
     pdf = product_target(z)
+    if str(z["target_kind"]) == "cpd":          # a cancelling sum: the error as a share of the sum's scale, not of max(1, |value|)
+        ref = rm.registration(pdf, z["grad_X"])
+        assert np.array_equal(ref["gr"], rm.gradient(pdf, z["grad_X"]))
+        assert share(z["grad"], ref["gr"], ref["gr_scale"]) < KAT_TOL
+        return
     assert rel(rm.gradient(pdf, z["grad_X"]), z["grad"]) < KAT_TOL
+
+
+# ------------------------------------------------------------------------------------------ the registration targets
+def share(got, want, scale):
+    """max |got - want| / scale, elementwise: the error as a share of the value's scale."""
+    return float(np.max(np.abs(np.asarray(got, dtype=rm.LD) - want) / scale))
+
+
+@pytest.mark.parametrize("name", REGISTRATION_KAT)
+def test_reproduces_recorded_registration_logprob(name):
+    """kat_q holds unit quaternions and rows of norm 0.5 .. 1.5: log_prob normalises."""
+    z = golden(f"traj_{name}.npz")
+    pdf = product_target(z)
+    ref = rm.registration(pdf, z["kat_q"], want_grad=False)
+    print(f"{name}: {share(z['kat_logp'], ref['lp'], ref['lp_scale']):.1e} of the scale, smallest neighbour gap {ref['gap']:.1e}")
+    assert share(z["kat_logp"], ref["lp"], ref["lp_scale"]) < KAT_TOL
+    assert np.array_equal(rm.log_prob(pdf, z["kat_q"]), ref["lp"]) and rm.log_prob(pdf, z["kat_q"][3]) == ref["lp"][3]
+
+
+@pytest.mark.parametrize("omega", [0.0, 0.2])
+@pytest.mark.parametrize("tag", ["3d", "2d"])
+def test_reproduces_recorded_cube_registration(tag, omega):
+    """helpers_kat.npz: the cube of the reference's own test, log_prob with a translation (the score of the target moved the
+    other way: it depends on the differences only, and the outlier box on the target's extent) and the gradient without."""
+    import geosss_amd as gs
+    z = golden("helpers_kat.npz")
+    cube = np.array([[x, y, zz] for zz in (-1, 1) for y in (-1, 1) for x in (-1, 1)], dtype=float)
+    src = gs.PointCloud(cube) if tag == "3d" else gs.RotationProjection(cube)
+    key = f"cpdt_{tag}_w{int(10 * omega)}"
+    qs = z["cpdt_qs"]
+    moved = gs.CoherentPointDrift(gs.PointCloud(z[f"cpdt_{tag}_target"] - z[f"cpdt_{tag}_t"]), src, sigma=0.5, k=8, omega=omega)
+    ref = rm.registration(moved, qs)
+    assert share(z[key + "_logp_qs"], ref["lp"], ref["lp_scale"]) < KAT_TOL
+    assert share(z[key + "_grad_qs"], ref["gr"], ref["gr_scale"]) < KAT_TOL
+    ref = rm.registration(gs.CoherentPointDrift(gs.PointCloud(z[f"cpdt_{tag}_target"]), src, sigma=0.5, k=8, omega=omega), qs)
+    assert share(z[key + "_grad_qs_not"], ref["gr"], ref["gr_scale"]) < KAT_TOL
+
+
+@pytest.mark.parametrize("model", ["gmm", "cpd"])
+@pytest.mark.parametrize("k", [1, 8, 9, 24])
+@pytest.mark.parametrize("tag", ["3d", "2d"])
+def test_reproduces_recorded_weighted_registration(tag, k, model):
+    """cpd_weighted_kat.npz: the reference's log_prob and gradient with non-uniform weights on both clouds."""
+    import geosss_amd as gs
+    z = golden("cpd_weighted_kat.npz")
+    assert k in z["ks"]
+    source = (gs.PointCloud if tag == "3d" else gs.RotationProjection)(z[f"{tag}_source"], z[f"{tag}_source_w"])
+    target = gs.PointCloud(z[f"{tag}_target"], z[f"{tag}_target_w"])
+    if model == "gmm":
+        pdf = gs.GaussianMixtureModel(target, source, float(z["sigma"]), k, beta=float(z["beta"]))
+    else:
+        pdf = gs.CoherentPointDrift(target, source, float(z["sigma"]), k, beta=float(z["beta"]), omega=float(z["omega"]))
+    ref = rm.registration(pdf, z[f"{tag}_q"])
+    e_lp = share(z[f"{tag}_k{k}_{model}_logp"], ref["lp"], ref["lp_scale"])
+    e_gr = share(z[f"{tag}_k{k}_{model}_grad"], ref["gr"], ref["gr_scale"])
+    print(f"{tag} k={k} {model}: {e_lp:.1e} (log_prob) {e_gr:.1e} (gradient) of the scale")
+    assert e_lp < KAT_TOL and e_gr < KAT_TOL
+
+
+@pytest.mark.parametrize("name", rc.CASES)
+def test_oracle_against_registration_reference(oracle, name):
+    """oracle.Target.cpd -- until now run on uniform weights only -- at every row of every case, on and off the sphere: 1e-12 of
+    the value's scale.  What that leaves to rounding: the oracle's d^2 carries a few 2^-53 of itself, so a term carries a few
+    2^-53 |term|, and gamma the same as a relative error."""
+    pdf, X, n_unit = rc.case(name)
+    ref = rc.reference(name)
+    tgt = rc.oracle_target(oracle, pdf)
+    e_lp, e_gr = rc.errors(tgt.log_prob(X), np.array([oracle.gradient(tgt, x) for x in X]), ref)
+    print(f"{name}: oracle {e_lp:.1e} (log_prob) {e_gr:.1e} (gradient) of the scale; neighbour gap {ref['gap']:.1e}, "
+          f"largest part of a term {ref['term']:.0f}")
+    assert abs(tgt.log_prob(X[5]) - float(ref["lp"][5])) <= KAT_TOL * float(ref["lp_scale"][5])
+    assert e_lp < KAT_TOL and e_gr < KAT_TOL
+    # a row and its negative: the same rotation, the opposite Jacobian
+    assert ref["lp"][2] == ref["lp"][3] and np.array_equal(ref["gr"][2], -ref["gr"][3])
+
+
+def test_registration_sweep_reaches_every_kernel_build():
+    """Each of the four builds (8 / 24 slots x uniform / weighted source) gets both target dimensions and both models."""
+    seen = {(rc.variant(s), s["dt"], s["model"]) for s in map(rc.spec, rc.SWEEP + ["k20_weighted"])}
+    assert seen >= {(v, dt, m) for v in range(4) for dt in (2, 3) for m in ("gmm", "cpd")}
+
+
+MP_CASES = ["one_point", "one_target_point", "ns24_k24", "sweep_2d_k9_wboth_cpd", "sweep_3d_k8_wsrc_gmm", "sharp_sigma"]
+
+
+@pytest.mark.parametrize("name", MP_CASES)
+def test_registration_longdouble_against_mpmath(name):
+    """The longdouble path against its mpmath twin, at 1e-17 of the largest term.  A term is log w - d^2 / (2 sigma^2) + const;
+    with T the largest of the three parts, longdouble holds it to T 2^-64 and no better, whatever it cancels to.  That is the
+    absolute error of a logsumexp, so log_prob is held to 1e-17 max(its scale, beta sum_l tw_l T); and it is the relative error of
+    exp(term - lse), of every gamma, so the gradient is held to 1e-17 max(1, T) of its scale."""
+    pdf, X, n_unit = rc.case(name)
+    pick = np.r_[0:4, n_unit:n_unit + 3]
+    ref = rm._registration_ld(pdf, X[pick], True)
+    lp_mp, gr_mp, _, _ = rm._registration_mp(pdf, X[pick])
+    T = max(1.0, ref["term"])
+    floor = T * float(pdf.beta) * float(np.sum(pdf.target.weights))
+    worst_lp = worst_gr = 0.0
+    with mpmath.workdps(rm.MP_DIGITS):
+        for i in range(len(pick)):
+            worst_lp = max(worst_lp, float(abs(_mp(ref["lp"][i]) - lp_mp[i]) / max(_mp(ref["lp_scale"][i]), floor)))
+            worst_gr = max(worst_gr, max(float(abs(_mp(a) - b) / _mp(s)) for a, b, s in zip(ref["gr"][i], gr_mp[i], ref["gr_scale"][i])) / T)
+        assert rm.log_prob_mp(pdf, X[pick[1]]) == lp_mp[1] and list(rm.gradient_mp(pdf, X[pick[1]])) == list(gr_mp[1])
+    print(f"{name}: longdouble against mpmath {worst_lp:.1e} (log_prob) {worst_gr:.1e} (gradient), largest part of a term {ref['term']:.0f}")
+    assert worst_lp <= 1e-17 and worst_gr <= 1e-17
 
 
 # ------------------------------------------------------------------------------------------ the oracle, at every d of the sweep
@@ -152,6 +264,16 @@ def test_longdouble_against_mpmath(family, d):
 def test_chain_margins(case, sampler):
     """No proposal of a reference chain of test_hip_mixture_layouts.py sits within 1e-8 of its threshold."""
     ref = lc.reference_chain(case, sampler)
+    print(f"{case} {sampler}: margin {ref['margin']:.2e}, tries {int(ref['tries'].sum())}, stride {ref['replay'].shape[1]}")
+    assert ref["margin"] > lc.MIN_MARGIN
+
+
+@pytest.mark.parametrize("sampler", ["shrink", "reject"])
+@pytest.mark.parametrize("case", rc.CHAIN_CASES)
+def test_registration_chain_margins(case, sampler):
+    """No proposal of a reference chain of test_hip_registration_reference.py sits within 1e-8 of its threshold (and none of its
+    evaluations met a near-tie of the k-th neighbour: reference_math asserts that of every one)."""
+    ref = rc.reference_chain(case, sampler)
     print(f"{case} {sampler}: margin {ref['margin']:.2e}, tries {int(ref['tries'].sum())}, stride {ref['replay'].shape[1]}")
     assert ref["margin"] > lc.MIN_MARGIN
 
