@@ -14,6 +14,7 @@ VARIANT_FAST_VERIFY = 101
 CHAIN_MAX_TRIES, CHAIN_NONFINITE, CHAIN_REPLAY_EXHAUSTED, CHAIN_COUNTER_SATURATED = 1, 2, 4, 8
 ABI_VERSION = 10
 STATS_NO_SECOND_MOMENT = 1
+MOMENTS_DIAG = 1
 
 
 class GsssError(RuntimeError):
@@ -61,6 +62,9 @@ SIGNATURES = {
     "gsss_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gsss_run": (C.c_int, [C.c_void_p, C.POINTER(RunArgs), C.c_void_p]),
     "gsss_stats_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gsss_moments_rows": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gsss_target_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p]),
     "gsss_last_launch": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gsss_batch_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

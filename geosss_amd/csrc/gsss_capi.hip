@@ -13,6 +13,7 @@
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
+#include "gsss_moments.h"
 #include "gsss_user_target.h"
 
 namespace gsss {
@@ -1213,6 +1214,48 @@ int64_t gsss_stats_rows(int32_t d, int32_t n_modes, int32_t n_lags, int32_t flag
     if (d < 2 || n_modes < 0 || n_lags < 0 || (flags & ~GSSS_STATS_NO_SECOND_MOMENT)) return GSSS_E_INVALID;
     const int64_t second = (flags & GSSS_STATS_NO_SECOND_MOMENT) ? 0 : (int64_t)d * (d + 1) / 2;
     return 1 + 2 * (int64_t)d + second + 2 + n_modes + 2 + 3 * (int64_t)n_lags;
+}
+
+int64_t gsss_moments_rows(int32_t d, int32_t flags)
+{
+    if (d < 2 || (flags & ~GSSS_MOMENTS_DIAG)) return GSSS_E_INVALID;
+    const bool diag = (flags & GSSS_MOMENTS_DIAG) != 0;
+    if (!diag && d > kMomentsMaxFullDim) return GSSS_E_UNSUPPORTED;
+    return 1 + moments_sums(d, diag);
+}
+
+int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_chains, int32_t d, int64_t samples_chain_rows,
+                        int64_t chains_per_target, int32_t flags, double *acc_dev, double *chain_sum_dev, int device, void *stream)
+{
+    if (d < 2 || (flags & ~GSSS_MOMENTS_DIAG)) {
+        set_error("gsss_target_moments: need d >= 2 and known flags (d = %d, flags = %d)", d, flags);
+        return GSSS_E_INVALID;
+    }
+    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
+        set_error("gsss_target_moments: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
+                  (long long)chains_per_target);
+        return GSSS_E_INVALID;
+    }
+    if (n_rows < 0 || samples_chain_rows < 0 || (samples_chain_rows > 0 && samples_chain_rows < n_rows)) {
+        set_error("gsss_target_moments: need n_rows >= 0 and samples_chain_rows 0 or >= n_rows (%lld rows, %lld per chain)",
+                  (long long)n_rows, (long long)samples_chain_rows);
+        return GSSS_E_INVALID;
+    }
+    if (!samples_dev || !acc_dev) {
+        set_error("gsss_target_moments: %s is null", samples_dev ? "acc_dev" : "samples_dev");
+        return GSSS_E_INVALID;
+    }
+    const bool diag = (flags & GSSS_MOMENTS_DIAG) != 0;
+    if (!diag && d > kMomentsMaxFullDim) {
+        set_error("gsss_target_moments: the full second-moment triangle is kept for d <= %d (d = %d): pass GSSS_MOMENTS_DIAG",
+                  kMomentsMaxFullDim, d);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    return launch_target_moments(samples_dev, n_rows, n_chains, d, samples_chain_rows, chains_per_target, diag, acc_dev, chain_sum_dev,
+                                 static_cast<hipStream_t>(stream));
 }
 
 int gsss_mode_supported(const gsss_target *t, int32_t mode)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 __all__ = ["acf", "acf_fft", "IAT", "n_eff", "distance", "hopping_frequency", "mode_occupancy", "mode_kl", "from_running",
-           "iat_from_acf", "ess_bulk", "ess_between_chains"]
+           "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments"]
 
 
 def _t(x):
@@ -247,6 +247,142 @@ def ess_between_chains(chain_means, n, chain_vars):
     tau = n_draws * between / total
     return {"tau": tau, "ess_per_chain": n_draws / tau, "ess_total": m.numel() * n_draws / tau,
             "rel_se": float(np.sqrt(2.0 / (m.numel() - 1))), "n": n_draws, "chains": int(m.numel())}
+
+
+def _moments_form(d, second_moment):
+    """(keep the full triangle?, accumulator rows per target) -- the rows of gsss_moments_rows."""
+    full = d <= 16 if second_moment is None else bool(second_moment)
+    if full and d > 16:
+        raise ValueError("the full second-moment triangle is kept for d <= 16: pass second_moment=False for the diagonal")
+    return full, 1 + d + (d * (d + 1) // 2 if full else d)
+
+
+def target_moments(x, chains_per_target, *, chain_major=False, second_moment=None, acc=None, chain_sum=None):
+    """Per-target sums of a block of draws on the device, in one pass and without atomics (gsss_target_moments, include/gsss.h).
+
+    x: a CUDA float64 tensor, component-major (R, d, n) -- what `advance(..., thin=t)` returns -- or, with chain_major=True,
+    (n, R, d) -- what `sample(..., as_tensor=True)` returns; a slice of rows of such an array is taken where it lies.  Target t
+    owns the chains [t m, (t + 1) m), m = chains_per_target.  Returns the accumulator (M, rows), M = n / m: row 0 the count of
+    draws, rows 1 .. d the sums of x_j, then the d (d + 1) / 2 sums of x_i x_j (i <= j, row-major; second_moment=None keeps them
+    for d <= 16) or, with second_moment=False, the d sums of x_j^2.  `acc` continues an earlier accumulator (added to, returned);
+    `chain_sum`, a (d, n) tensor, has every chain's sum of its R draws added to it."""
+    from . import _lib
+    from .sphere import current_stream_ptr
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64 or x.ndim != 3:
+        raise ValueError("x must be a CUDA float64 tensor (R, d, n), or (n, R, d) with chain_major=True")
+    m = int(chains_per_target)
+    if chain_major:
+        n, R, d = (int(v) for v in x.shape)
+        if n * R and not (x.stride(2) == 1 and x.stride(1) == d and x.stride(0) % d == 0 and x.stride(0) >= R * d):
+            x = x.contiguous()
+        chain_rows = int(x.stride(0)) // d if n * R else max(R, 1)
+    else:
+        R, d, n = (int(v) for v in x.shape)
+        x, chain_rows = x.contiguous(), 0
+    full, rows = _moments_form(d, second_moment)
+    if m < 1 or n % m:
+        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+    M = n // m
+    if acc is None:
+        acc = torch.zeros((M, rows), dtype=torch.float64, device=x.device)
+    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (M, rows) or acc.dtype != torch.float64 or acc.device != x.device
+          or not acc.is_contiguous()):
+        raise ValueError(f"acc must be a contiguous float64 tensor ({M}, {rows}) on the device of x")
+    if chain_sum is not None and (not isinstance(chain_sum, torch.Tensor) or tuple(chain_sum.shape) != (d, n)
+                                  or chain_sum.dtype != torch.float64 or chain_sum.device != x.device
+                                  or not chain_sum.is_contiguous()):
+        raise ValueError(f"chain_sum must be a contiguous float64 tensor ({d}, {n}) on the device of x")
+    if R == 0 or n == 0:
+        return acc
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsss_target_moments(x.data_ptr(), R, n, d, chain_rows, m, 0 if full else _lib.MOMENTS_DIAG,
+                                                   acc.data_ptr(), None if chain_sum is None else chain_sum.data_ptr(), dev,
+                                                   current_stream_ptr(dev)))
+    return acc
+
+
+def from_target_moments(acc, d, *, chain_sum=None, chains_per_target=None, second_moment=True):
+    """Per-target summaries from the accumulators of `target_moments` / `Sampler.summarize`; every entry has the leading axis M.
+    With N = acc[:, 0] draws per target, S_j = sum x_j and Q_ij = sum x_i x_j:
+
+        n = N,  mean_j = S_j / N,  second_moment_ij = Q_ij / N (symmetric; second_moment=False: second_moment_diag_j = Q_jj / N),
+        cov = second_moment - mean mean^T,  var_j = Q_jj / N - mean_j^2 (biased, 1 / N),
+        resultant_length = |mean|,  mean_direction = mean / |mean|.
+
+    With chain_sum (d, n) and m = chains_per_target, the chains of a target are compared, per coordinate j.  A chain has
+    r = N / m draws and the mean c = chain_sum / r; over the m chains of the target
+
+        between_j = (sum c^2 - (sum c)^2 / m) / (m - 1)        the unbiased variance of the chain means,
+        within_j  = Q_jj / N - (sum c^2) / m                    the mean of the chains' own (biased, 1 / r) variances,
+        rhat_j    = sqrt((within_j + between_j) / (within_j r / (r - 1)))     Gelman-Rubin: var+ = (r - 1) / r W + B / r over W
+                                                                with W = within r / (r - 1) and B / r = between,
+        ess_between_j = (within_j + between_j) / between_j      ess_between_chains' "ess_per_chain": pooled variance over the
+                                                                variance of the chain means.
+
+    On CUDA tensors sum c and sum c^2 come from the moments kernel itself, run on the one row of chain means; CPU tensors take
+    the same sums with torch."""
+    acc = _t(acc).to(torch.float64)
+    M = acc.shape[0]
+    n = acc[:, 0]
+    mean = acc[:, 1:1 + d] / n[:, None]
+    out = {"n": n, "mean": mean}
+    if second_moment:
+        T = d * (d + 1) // 2
+        iu = torch.triu_indices(d, d, device=acc.device)
+        q = acc[:, 1 + d:1 + d + T] / n[:, None]
+        sm = torch.zeros((M, d, d), dtype=torch.float64, device=acc.device)
+        sm[:, iu[0], iu[1]] = q
+        sm[:, iu[1], iu[0]] = q
+        out["second_moment"] = sm
+        out["cov"] = sm - mean[:, :, None] * mean[:, None, :]
+        qd = torch.diagonal(sm, dim1=1, dim2=2)
+    else:
+        qd = acc[:, 1 + d:1 + 2 * d] / n[:, None]
+        out["second_moment_diag"] = qd
+    out["var"] = qd - mean * mean
+    rl = torch.linalg.norm(mean, dim=1)
+    out["resultant_length"] = rl
+    out["mean_direction"] = mean / rl[:, None]
+    if chain_sum is None:
+        return out
+    if chains_per_target is None:
+        raise ValueError("chain_sum needs chains_per_target")
+    m = int(chains_per_target)
+    cs = _t(chain_sum).to(torch.float64)
+    if cs.ndim != 2 or cs.shape[0] != d or cs.shape[1] != M * m:
+        raise ValueError(f"chain_sum must be (d, n) = ({d}, {M * m})")
+    r = n / m                                                        # draws per chain
+    cm = (cs.reshape(d, M, m) / r[None, :, None]).reshape(1, d, M * m)
+    if cm.is_cuda:
+        a2 = target_moments(cm, m, second_moment=False)               # the same kernel on the row of chain means
+        s1, s2 = a2[:, 1:1 + d], a2[:, 1 + d:1 + 2 * d]
+    else:
+        c3 = cm.reshape(d, M, m)
+        s1, s2 = c3.sum(-1).T, (c3 * c3).sum(-1).T
+    between = (s2 - s1 * s1 / m) / (m - 1) if m > 1 else torch.full_like(s1, float("nan"))
+    within = qd - s2 / m
+    out["between"], out["within"] = between, within
+    out["rhat"] = torch.sqrt((within + between) / (within * (r / (r - 1))[:, None]))
+    out["ess_between"] = (within + between) / between
+    return out
+
+
+class TargetMoments:
+    """What `Sampler.summarize` returns: the per-target accumulators of a run (`acc` (M, rows), `chain_sum` (d, n), device
+    tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`."""
+
+    def __init__(self, acc, chain_sum, d, chains_per_target, second_moment):
+        self.acc, self.chain_sum, self.d = acc, chain_sum, int(d)
+        self.chains_per_target, self.second_moment = int(chains_per_target), bool(second_moment)
+
+    @property
+    def n_targets(self):
+        return int(self.acc.shape[0])
+
+    def stats(self):
+        return from_target_moments(self.acc, self.d, chain_sum=self.chain_sum, chains_per_target=self.chains_per_target,
+                                   second_moment=self.second_moment)
 
 
 def _average_ranks(flat):

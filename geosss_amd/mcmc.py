@@ -618,6 +618,65 @@ class RejectionSphericalSliceSampler:
         self._sync_rng()
         return out[0] if self._single else out
 
+    def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None):
+        """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
+        would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
+        windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
+        folded into per-target accumulators by the moments kernel (gsss_target_moments: one pass, no atomics).  Works behind
+        every kernel family, mode and dimension, a TargetBatch included.  window=None: the rows that keep the buffer at or
+        under 256 MiB.  Target t owns chains [t m, (t + 1) m): m is the batch's for a TargetBatch (a sampler on a run of the
+        targets summarises its own, as rows 0 .. of the result); for a single target m = chains_per_target, by default all
+        chains: the pooled ensemble moments and R-hat over all chains.  second_moment: keep the full triangle (None: for
+        d <= 16), else the diagonal.  Returns a diagnostics.TargetMoments (.acc, .chain_sum, .stats()); into= continues an
+        earlier one (pass burnin=thin to go on where that run's last draw was taken).  Call accounting, error checking and the
+        final state are those of the equivalent advance() calls."""
+        from . import diagnostics
+        if not n_samples > 0:
+            raise AssertionError("n_samples must be positive")
+        burnin = determine_burnin(n_samples, burnin)
+        thin = int(thin)
+        if thin < 1:
+            raise ValueError("thin must be >= 1")
+        n, d = self.n_chains, self.d
+        if self._batch_m is not None:
+            if chains_per_target is not None and int(chains_per_target) != self._batch_m:
+                raise ValueError(f"this sampler's TargetBatch has {self._batch_m} chains per target")
+            m = self._batch_m
+        else:
+            m = n if chains_per_target is None else int(chains_per_target)
+        if m < 1 or n % m:
+            raise ValueError(f"n_chains ({n}) must be a multiple of chains_per_target ({m})")
+        full, rows = diagnostics._moments_form(d, second_moment if into is None or second_moment is not None else into.second_moment)
+        if into is None:
+            into = diagnostics.TargetMoments(torch.zeros((n // m, rows), dtype=torch.float64, device=self._tdev),
+                                             torch.zeros((d, n), dtype=torch.float64, device=self._tdev), d, m, full)
+        elif (into.d != d or into.chains_per_target != m or into.second_moment != full or tuple(into.acc.shape) != (n // m, rows)
+              or tuple(into.chain_sum.shape) != (d, n)):
+            raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
+        rest = int(n_samples) - 1
+        window = max(1, (256 << 20) // (8 * d * n)) if window is None else int(window)
+        if window < 1:
+            raise ValueError("window must be >= 1")
+        window = max(1, min(window, rest))
+        steps0 = self._step
+        if burnin:
+            self.advance(burnin)
+
+        def fold(x):
+            diagnostics.target_moments(x, m, second_moment=full, acc=into.acc, chain_sum=into.chain_sum)
+
+        fold(self._state[None])                       # draw 0: the state itself is a (1, d, n) window
+        buf = torch.empty((window, d, n), dtype=torch.float64, device=self._tdev) if rest else None
+        done = 0
+        while done < rest:
+            w = min(window, rest - done)
+            fold(self.advance(w * thin, thin=thin, out=buf[:w]))
+            done += w
+        self._account_calls(self._step - steps0)
+        self._check_errors()
+        self._sync_rng()
+        return into
+
     def _sample_rows(self, out, skip, n_rows, thin):
         """burn-in, row 0 = the state after it, then the kept rows, written straight into `out` (chains, draws, dims)."""
         if skip:
@@ -811,6 +870,9 @@ class MetropolisHastings(RejectionSphericalSliceSampler):
 
     def enable_stats(self, *a, **k):
         raise ValueError("running statistics are accumulated by the slice-sampler kernels")
+
+    def summarize(self, *a, **k):
+        raise ValueError("summarize() belongs to the slice samplers")
 
     def state_dict(self):
         d = super().state_dict()

@@ -314,6 +314,30 @@ int gsss_batch_plan(int32_t kind, int32_t d, int32_t k, int32_t has_b, int64_t n
 /* Number of rows of gsss_run_args.stats_dev for dimension d, K modes, L lags and the GSSS_STATS_* flags (< 0: bad argument). */
 int64_t gsss_stats_rows(int32_t d, int32_t n_modes, int32_t n_lags, int32_t flags);
 
+/* Per-TARGET moments of a block of retained draws, for ensembles in which target t owns the chains [t m, (t + 1) m),
+ * m = chains_per_target (a gsss_target_create_batch handle's chains; m = n_chains pools one target's whole ensemble): what
+ * gsss_run_args.stats_dev cannot give a batch.  The block is what gsss_run wrote to samples_dev -- component-major
+ * [n_rows][d][n_chains] (samples_chain_rows 0) or rows 0 .. n_rows - 1 of every chain's run of samples_chain_rows rows in a
+ * [n_chains][samples_chain_rows][d] array (offset the pointer by row0 * d doubles, as for gsss_run) -- read once, by a kernel of its
+ * own beside the sampler, so it serves every kernel family, mode and dimension.  Any m >= 1 that divides n_chains.
+ * acc_dev [n_chains / m][gsss_moments_rows(d, flags)], ADDED to (zero it before the first block), per target:
+ *     0                count of draws: m * n_rows per call
+ *     1 .. d           sum of x_j
+ *     .. + T           sum of x_i x_j, i <= j, row-major upper triangle (the order of stats_dev), T = d (d + 1) / 2, d <= 16;
+ *                      with GSSS_MOMENTS_DIAG the d sums of x_j^2 instead (any d)
+ * chain_sum_dev: NULL or [d][n_chains], ADDED to: every chain's sum of its rows of the block -- divided by the draws they are the
+ * chain means, whose per-target sums and sums of squares (the between-chain variance of R-hat) are one more call of this function
+ * with n_rows = 1 and GSSS_MOMENTS_DIAG (geosss_amd/diagnostics.py from_target_moments).
+ * No floating-point atomics: the order of every sum is fixed by the arguments, so a call gives the same bits every time.
+ * GSSS_E_INVALID: d < 2, m < 1, n_chains no multiple of m, a negative row count, 0 < samples_chain_rows < n_rows, a NULL
+ * samples_dev / acc_dev, unknown flags; GSSS_E_UNSUPPORTED: the full triangle at d > 16 (gsss_moments_rows returns the same
+ * codes) -- all of them before the device is touched.  n_rows = 0 does nothing.  The reference computes such summaries on the host
+ * from stored chains (scripts/bingham.py, scripts/vMF_diagnostics.py); nothing there works without the stored draws. */
+#define GSSS_MOMENTS_DIAG 1
+int64_t gsss_moments_rows(int32_t d, int32_t flags);
+int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_chains, int32_t d, int64_t samples_chain_rows,
+                        int64_t chains_per_target, int32_t flags, double *acc_dev, double *chain_sum_dev, int device, void *stream);
+
 /* 1 if gsss_run accepts `mode` for this target's shape (fast mode is built for the shapes listed in
  * geosss_amd/csrc/gsss_fast_*.hip), else 0. */
 int gsss_mode_supported(const gsss_target *t, int32_t mode);
