@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "gsss_batch.h"
+#include "gsss_batch_logprob.h"
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
@@ -951,6 +952,73 @@ int gsss_gradient(const gsss_target *t, const double *x_dev, int64_t n, double *
     return logprob_or_gradient(t, x_dev, n, grad_dev, true, stream);
 }
 
+// every member of a batch handle at its own rows of x_dev [M][n][d]
+static int batch_logprob_or_gradient(const gsss_target *t, const double *x_dev, int64_t n, double *out_dev, bool grad, void *stream)
+{
+    const char *fn = grad ? "gsss_batch_gradient" : "gsss_batch_logprob";
+    if (!t || n < 0) {
+        set_error("%s: %s", fn, t ? "n_per_target must be >= 0" : "null handle");
+        return GSSS_E_INVALID;
+    }
+    if (!is_batch(t)) {
+        set_error("%s takes a gsss_target_create_batch handle: a single target is evaluated by %s", fn, grad ? "gsss_gradient" : "gsss_logprob");
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (n == 0) return GSSS_OK;
+    if (!x_dev || !out_dev) {
+        set_error("%s: %s is null", fn, x_dev ? "the output" : "x_dev");
+        return GSSS_E_INVALID;
+    }
+    const int vec = select_vec_for(t->tb, 0);
+    if (vec < 0) return vec;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return GSSS_E_HIP;
+    return launch_batch_logprob(vec, t->tb, batch_points_rows(x_dev, out_dev, n, t->tb.d, t->batch.stride), t->batch.n_targets, grad,
+                                static_cast<hipStream_t>(stream));
+}
+
+int gsss_batch_logprob(const gsss_target *t, const double *x_dev, int64_t n_per_target, double *out_dev, void *stream)
+{
+    return batch_logprob_or_gradient(t, x_dev, n_per_target, out_dev, false, stream);
+}
+
+int gsss_batch_gradient(const gsss_target *t, const double *x_dev, int64_t n_per_target, double *grad_dev, void *stream)
+{
+    return batch_logprob_or_gradient(t, x_dev, n_per_target, grad_dev, true, stream);
+}
+
+int gsss_batch_logprob_draws(const gsss_target *t, const double *samples_dev, int64_t n_rows, int64_t n_chains, int64_t target0,
+                             double *out_dev, void *stream)
+{
+    if (!t || n_rows < 0 || n_chains < 0 || target0 < 0) {
+        set_error("gsss_batch_logprob_draws: %s", t ? "n_rows, n_chains and target0 must be >= 0" : "null handle");
+        return GSSS_E_INVALID;
+    }
+    if (!is_batch(t)) {
+        set_error("gsss_batch_logprob_draws takes a gsss_target_create_batch handle");
+        return GSSS_E_UNSUPPORTED;
+    }
+    const int64_t m = t->batch.m;
+    if (n_chains % m != 0 || target0 > t->batch.n_targets || n_chains / m > t->batch.n_targets - target0) {
+        set_error("gsss_batch_logprob_draws: %lld chains from target %lld on are no run of whole targets of the batch (%lld chains per "
+                  "target, %d targets)", (long long)n_chains, (long long)target0, (long long)m, t->batch.n_targets);
+        return GSSS_E_INVALID;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    if (!samples_dev || !out_dev) {
+        set_error("gsss_batch_logprob_draws: %s is null", samples_dev ? "out_dev" : "samples_dev");
+        return GSSS_E_INVALID;
+    }
+    const int vec = select_vec_for(t->tb, 0);
+    if (vec < 0) return vec;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return GSSS_E_HIP;
+    TargetBlock tbb = t->tb;
+    tbb.blob += target0 * t->batch.stride;
+    return launch_batch_logprob(vec, tbb, batch_points_draws(samples_dev, out_dev, n_rows, n_chains, m, tbb.d, t->batch.stride),
+                                n_chains / m, false, static_cast<hipStream_t>(stream));
+}
+
 int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
 {
     if (!t || !a) {
@@ -1255,6 +1323,30 @@ int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_cha
     DeviceGuard guard(device);
     if (!guard.ok) return GSSS_E_HIP;
     return launch_target_moments(samples_dev, n_rows, n_chains, d, samples_chain_rows, chains_per_target, diag, acc_dev, chain_sum_dev,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int gsss_scalar_moments(const double *values_dev, int64_t n_rows, int64_t n_chains, int64_t chains_per_target, double *acc_dev,
+                        double *chain_sum_dev, int device, void *stream)
+{
+    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
+        set_error("gsss_scalar_moments: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
+                  (long long)chains_per_target);
+        return GSSS_E_INVALID;
+    }
+    if (n_rows < 0) {
+        set_error("gsss_scalar_moments: need n_rows >= 0 (%lld)", (long long)n_rows);
+        return GSSS_E_INVALID;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    if (!values_dev || !acc_dev) {
+        set_error("gsss_scalar_moments: %s is null", values_dev ? "acc_dev" : "values_dev");
+        return GSSS_E_INVALID;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    // [n_rows][1][n_chains] through the any-d diagonal kernel: acc rows count, sum v, sum v^2
+    return launch_target_moments(values_dev, n_rows, n_chains, 1, 0, chains_per_target, true, acc_dev, chain_sum_dev,
                                  static_cast<hipStream_t>(stream));
 }
 

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 __all__ = ["acf", "acf_fft", "IAT", "n_eff", "distance", "hopping_frequency", "mode_occupancy", "mode_kl", "from_running",
-           "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments"]
+           "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments",
+           "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw"]
 
 
 def _t(x):
@@ -368,21 +369,148 @@ def from_target_moments(acc, d, *, chain_sum=None, chains_per_target=None, secon
     return out
 
 
+def target_log_prob(batch, x, *, chain_major=False, target0=0):
+    """log_prob of a block of draws under the targets of a TargetBatch that own them, in one launch and where the draws lie
+    (gsss_batch_logprob_draws, include/gsss.h).
+
+    x: a CUDA float64 tensor, component-major (R, d, N) -- what `advance(..., thin=t)` returns -- -> (R, N); or, with
+    chain_major=True, (N, R, d) -- what `sample(..., as_tensor=True)` returns -- -> (N, R).  The block covers the targets
+    target0 .. len(batch) - 1, each with the same number of chains: m = N / (len(batch) - target0), which must divide; chain c
+    belongs to target target0 + c // m.  The values are the members' own `log_prob`, bit for bit."""
+    from . import _lib
+    from .sphere import current_stream_ptr
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64 or x.ndim != 3:
+        raise ValueError("x must be a CUDA float64 tensor (R, d, N), or (N, R, d) with chain_major=True")
+    N, R, d = (int(v) for v in (x.shape if chain_major else (x.shape[2], x.shape[0], x.shape[1])))
+    M, target0 = len(batch), int(target0)
+    if d != batch.d:
+        raise ValueError(f"the batch's targets live in d={batch.d} (got {d})")
+    if not 0 <= target0 < M:
+        raise ValueError(f"target0 ({target0}) must be one of the batch's {M} targets")
+    covered = M - target0
+    if N < covered or N % covered:
+        raise ValueError(f"the number of chains ({N}) must be a multiple of the {covered} targets covered (target0 = {target0} .. "
+                         f"{M - 1}), with at least one chain each")
+    m = N // covered
+    out = torch.empty((N, R) if chain_major else (R, N), dtype=torch.float64, device=x.device)
+    if R == 0:
+        return out
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    tgt = batch._device_target(x.device, chains_per_target=m)
+    with torch.cuda.device(dev):
+        if chain_major and target0 == 0:   # (N, R, d) is row-major (M, m R, d): every member at its own rows
+            x = x.contiguous()
+            _lib.check(tgt.lib.gsss_batch_logprob(tgt.handle, x.data_ptr(), m * R, out.data_ptr(), current_stream_ptr(dev)))
+            return out
+        xc = x.permute(1, 2, 0).contiguous() if chain_major else x.contiguous()
+        oc = torch.empty((R, N), dtype=torch.float64, device=x.device) if chain_major else out
+        _lib.check(tgt.lib.gsss_batch_logprob_draws(tgt.handle, xc.data_ptr(), R, N, target0, oc.data_ptr(), current_stream_ptr(dev)))
+    if chain_major:
+        out.copy_(oc.t())
+    return out
+
+
+def scalar_moments(values, chains_per_target, *, acc=None, chain_sum=None):
+    """`target_moments` for one scalar per draw (gsss_scalar_moments): values (R, N), a CUDA float64 tensor, target t owning the
+    chains [t m, (t + 1) m).  Returns acc (M, 3): count, sum v, sum v^2 -- `acc` continues an earlier one; `chain_sum` (N,) has
+    every chain's sum of its R values added to it.  The same kernels, the same fixed summation order."""
+    from . import _lib
+    from .sphere import current_stream_ptr
+    if not isinstance(values, torch.Tensor) or not values.is_cuda or values.dtype != torch.float64 or values.ndim != 2:
+        raise ValueError("values must be a CUDA float64 tensor (R, N)")
+    values = values.contiguous()
+    R, N = (int(v) for v in values.shape)
+    m = int(chains_per_target)
+    if m < 1 or N % m:
+        raise ValueError(f"the number of chains ({N}) must be a multiple of chains_per_target ({chains_per_target})")
+    if acc is None:
+        acc = torch.zeros((N // m, 3), dtype=torch.float64, device=values.device)
+    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (N // m, 3) or acc.dtype != torch.float64
+          or acc.device != values.device or not acc.is_contiguous()):
+        raise ValueError(f"acc must be a contiguous float64 tensor ({N // m}, 3) on the device of the values")
+    if chain_sum is not None and (not isinstance(chain_sum, torch.Tensor) or tuple(chain_sum.shape) != (N,)
+                                  or chain_sum.dtype != torch.float64 or chain_sum.device != values.device
+                                  or not chain_sum.is_contiguous()):
+        raise ValueError(f"chain_sum must be a contiguous float64 tensor ({N},) on the device of the values")
+    if R == 0 or N == 0:
+        return acc
+    dev = values.device.index if values.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsss_scalar_moments(values.data_ptr(), R, N, m, acc.data_ptr(),
+                                                   None if chain_sum is None else chain_sum.data_ptr(), dev, current_stream_ptr(dev)))
+    return acc
+
+
+def best_draw(values, chains_per_target):
+    """The largest value per target of a block values (R, N), target t owning the chains [t m, (t + 1) m), and where it is:
+    -> (best (M,), row (M,), chain (M,)), chain in 0 .. N - 1.  Ties go to the earliest row, then to the lowest chain (the
+    first occurrence in (row, chain) order, found as the smallest index that attains the maximum: the same on every device)."""
+    v = _t(values)
+    R, N = (int(s) for s in v.shape)
+    m = int(chains_per_target)
+    M = N // m
+    flat = v.reshape(R, M, m).permute(1, 0, 2).reshape(M, R * m)      # index: row m + chain of the target
+    best = flat.amax(dim=1)
+    pos = torch.arange(R * m, device=v.device)
+    first = torch.where(flat == best[:, None], pos[None, :], R * m - 1).amin(dim=1)
+    return best, first // m, torch.arange(M, device=v.device) * m + first % m
+
+
+def from_scalar_moments(acc, chain_sum, chains_per_target):
+    """`from_target_moments` for one scalar per draw: acc (M, 3) = count N, S = sum v, Q = sum v^2, chain_sum (M m,).  With
+    r = N / m draws a chain and c = chain_sum / r the chain means:  mean = S / N,  var = Q / N - mean^2 (biased),
+    between = (sum c^2 - (sum c)^2 / m) / (m - 1),  within = Q / N - (sum c^2) / m,
+    rhat = sqrt((within + between) / (within r / (r - 1))),  ess_between = (within + between) / between.  CPU or CUDA tensors."""
+    acc = _t(acc).to(torch.float64)
+    m = int(chains_per_target)
+    M = acc.shape[0]
+    n = acc[:, 0]
+    mean, q = acc[:, 1] / n, acc[:, 2] / n
+    r = n / m
+    cm = _t(chain_sum).to(torch.float64).reshape(M, m) / r[:, None]
+    s1, s2 = cm.sum(-1), (cm * cm).sum(-1)
+    between = (s2 - s1 * s1 / m) / (m - 1) if m > 1 else torch.full_like(s1, float("nan"))
+    within = q - s2 / m
+    return {"mean": mean, "var": q - mean * mean, "between": between, "within": within,
+            "rhat": torch.sqrt((within + between) / (within * (r / (r - 1)))), "ess_between": (within + between) / between}
+
+
 class TargetMoments:
     """What `Sampler.summarize` returns: the per-target accumulators of a run (`acc` (M, rows), `chain_sum` (d, n), device
-    tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`."""
+    tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`.
 
-    def __init__(self, acc, chain_sum, d, chains_per_target, second_moment):
+    With `summarize(log_prob=True)` also the log-density trace: `lp_acc` (M, 3) -- count, sum, sum of squares of log_prob over
+    the target's draws --, `lp_chain_sum` (n,), and the best draw seen per target, `lp_best` (M,) and `x_best` (M, d): the maximum
+    of log_prob over all retained draws (ties: the earliest draw, then the lowest chain).  stats() then adds lp_mean, lp_var,
+    lp_rhat, lp_ess_between (`from_scalar_moments`), lp_best and x_best."""
+
+    def __init__(self, acc, chain_sum, d, chains_per_target, second_moment, lp_acc=None, lp_chain_sum=None, lp_best=None,
+                 x_best=None):
         self.acc, self.chain_sum, self.d = acc, chain_sum, int(d)
         self.chains_per_target, self.second_moment = int(chains_per_target), bool(second_moment)
+        self.lp_acc, self.lp_chain_sum, self.lp_best, self.x_best = lp_acc, lp_chain_sum, lp_best, x_best
 
     @property
     def n_targets(self):
         return int(self.acc.shape[0])
 
+    def update_best(self, values, x):
+        """Fold a window into the running best draw: values (w, n) the log_prob of the draws x (w, d, n).  A later draw replaces
+        the best only if it is strictly better."""
+        best, row, chain = best_draw(values, self.chains_per_target)
+        better = best > self.lp_best
+        self.lp_best = torch.where(better, best, self.lp_best)
+        self.x_best = torch.where(better[:, None], x[row, :, chain], self.x_best)
+
     def stats(self):
-        return from_target_moments(self.acc, self.d, chain_sum=self.chain_sum, chains_per_target=self.chains_per_target,
-                                   second_moment=self.second_moment)
+        out = from_target_moments(self.acc, self.d, chain_sum=self.chain_sum, chains_per_target=self.chains_per_target,
+                                  second_moment=self.second_moment)
+        if self.lp_acc is not None:
+            lp = from_scalar_moments(self.lp_acc, self.lp_chain_sum, self.chains_per_target)
+            out.update(lp_mean=lp["mean"], lp_var=lp["var"], lp_rhat=lp["rhat"], lp_ess_between=lp["ess_between"])
+        if self.lp_best is not None:
+            out.update(lp_best=self.lp_best, x_best=self.x_best)
+        return out
 
 
 def _average_ranks(flat):

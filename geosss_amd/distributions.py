@@ -434,8 +434,8 @@ class TargetBatch(Distribution):
     `BinghamFisher` (all with or all without b; `Uniform(d)` is a Bingham with A = 0), of one dimension.  A batch whose members
     are all diagonal-A Bingham runs the diagonal fast kernels, a batch that mixes diagonal and dense A the dense ones.
     Samplers: the two slice samplers on the library (Philox) stream; the Metropolis-Hastings / HMC classes, rng='numpy',
-    replay and running statistics are refused.  `log_prob` / `gradient` take (M, n, d) and return (M, n) / (M, n, d), member
-    by member.  Editing a member's parameters re-uploads the batch, as for MixtureModel."""
+    replay and running statistics are refused.  `log_prob` / `gradient` take (M, n, d) and return (M, n) / (M, n, d): every
+    member at its own rows, in one launch.  Editing a member's parameters re-uploads the batch, as for MixtureModel."""
 
     def __init__(self, pdfs):
         self.pdfs = list(pdfs)
@@ -525,26 +525,53 @@ class TargetBatch(Distribution):
                                                C.byref(grid), C.byref(use)))
         return {"chains_per_workgroup": cpw.value, "targets_per_workgroup": tpw.value, "grid": grid.value, "lane_use": use.value}
 
-    def _per_member(self, x, what):
+    def _batch_handle(self, device=None):
+        """A device copy of the batch for evaluation: any cached one of the device whose parameters are current (the members'
+        blobs do not depend on the chains per target), else a new one with one chain per target."""
+        dev = _device_index(device)
+        key = self._device_key(self._pack(1))
+        for (cdev, _), (ckey, tgt) in self.__dict__.get("_targets", {}).items():
+            if cdev == dev and ckey[:5] == key[:5] and ckey[6:] == key[6:]:
+                return tgt
+        return self._device_target(dev, 1)
+
+    def _evaluate(self, x, grad):
+        """One launch on the batch handle (gsss_batch_logprob / gsss_batch_gradient): x (M, n, d), numpy or a CUDA tensor."""
         M, d = len(self.pdfs), self.d
+        what = "gradient" if grad else "log_prob"
         if isinstance(x, torch.Tensor):
             if x.ndim != 3 or x.shape[0] != M or x.shape[2] != d:
                 raise ValueError(f"expected (M, n, d) input with M={M}, d={d}")
-            return torch.stack([getattr(p, what)(x[t].contiguous()) for t, p in enumerate(self.pdfs)])
+            if not x.is_cuda:
+                raise ValueError(f"torch input to {what} must live on the GPU")
+            xt = x.to(torch.float64).contiguous()
+            n = int(xt.shape[1])
+            out = torch.empty_like(xt) if grad else torch.empty((M, n), dtype=torch.float64, device=xt.device)
+            if n == 0:
+                return out
+            dev = _device_index(xt.device)
+            tgt = self._batch_handle(xt.device)
+            fn = tgt.lib.gsss_batch_gradient if grad else tgt.lib.gsss_batch_logprob
+            with torch.cuda.device(dev):
+                _lib.check(fn(tgt.handle, xt.data_ptr(), n, out.data_ptr(), current_stream_ptr(dev)))
+            return out
         x = np.asarray(x, dtype=np.float64)
         if x.ndim != 3 or x.shape[0] != M or x.shape[2] != d:
             raise ValueError(f"expected (M, n, d) input with M={M}, d={d}")
-        return np.stack([np.asarray(getattr(p, what)(x[t])) for t, p in enumerate(self.pdfs)])
+        _lib.require_device()
+        dev = _device_index(None)
+        return self._evaluate(torch.from_numpy(np.ascontiguousarray(x)).to(f"cuda:{dev}"), grad).cpu().numpy()
 
     @counted
     def log_prob(self, x):
-        """x (M, n, d) -> (M, n): member t's log_prob of its own rows x[t], each evaluated on the device."""
-        return self._per_member(x, "_log_prob_device")
+        """x (M, n, d) -> (M, n): member t's log_prob of its own rows x[t], all members in one launch on the batch's own device
+        copy (no member is uploaded); the values are the members' own, bit for bit."""
+        return self._evaluate(x, False)
 
     @counted
     def gradient(self, x):
-        """x (M, n, d) -> (M, n, d): member t's gradient (as its class defines it) at its own rows, on the device."""
-        return self._per_member(x, "_gradient_device")
+        """x (M, n, d) -> (M, n, d): member t's gradient (as the device evaluates its family's) at its own rows, in one launch."""
+        return self._evaluate(x, True)
 
 
 class Bingham(Distribution):

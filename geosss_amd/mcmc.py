@@ -618,7 +618,8 @@ class RejectionSphericalSliceSampler:
         self._sync_rng()
         return out[0] if self._single else out
 
-    def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None):
+    def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None,
+                  log_prob=False):
         """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
         would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
         windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
@@ -629,7 +630,14 @@ class RejectionSphericalSliceSampler:
         chains: the pooled ensemble moments and R-hat over all chains.  second_moment: keep the full triangle (None: for
         d <= 16), else the diagonal.  Returns a diagnostics.TargetMoments (.acc, .chain_sum, .stats()); into= continues an
         earlier one (pass burnin=thin to go on where that run's last draw was taken).  Call accounting, error checking and the
-        final state are those of the equivalent advance() calls."""
+        final state are those of the equivalent advance() calls.
+
+        log_prob=True (a TargetBatch sampler): every window, draw 0 included, is also evaluated under the targets that own its
+        chains (gsss_batch_logprob_draws, one launch) into one reused (window, n) buffer, which is folded into `lp_acc` and
+        `lp_chain_sum` (gsss_scalar_moments) and into the running best draw per target, `lp_best` / `x_best` -- the MAP estimate
+        among the retained draws; stats() then reports lp_mean, lp_var, lp_rhat, lp_ess_between, lp_best, x_best.  into=
+        continues them too (a summary that carries them goes on carrying them); one begun without cannot take them up.  The
+        moments, the chains and the launches of the default are untouched by it."""
         from . import diagnostics
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")
@@ -646,13 +654,24 @@ class RejectionSphericalSliceSampler:
             m = n if chains_per_target is None else int(chains_per_target)
         if m < 1 or n % m:
             raise ValueError(f"n_chains ({n}) must be a multiple of chains_per_target ({m})")
+        if log_prob and self._batch_m is None:
+            raise ValueError("summarize(log_prob=True) evaluates the draws with the batch kernel: wrap the target in a TargetBatch "
+                             "of one (TargetBatch([pdf]), chains_per_target = n_chains)")
         full, rows = diagnostics._moments_form(d, second_moment if into is None or second_moment is not None else into.second_moment)
         if into is None:
             into = diagnostics.TargetMoments(torch.zeros((n // m, rows), dtype=torch.float64, device=self._tdev),
                                              torch.zeros((d, n), dtype=torch.float64, device=self._tdev), d, m, full)
+            if log_prob:
+                into.lp_acc = torch.zeros((n // m, 3), dtype=torch.float64, device=self._tdev)
+                into.lp_chain_sum = torch.zeros(n, dtype=torch.float64, device=self._tdev)
+                into.lp_best = torch.full((n // m,), float("-inf"), dtype=torch.float64, device=self._tdev)
+                into.x_best = torch.zeros((n // m, d), dtype=torch.float64, device=self._tdev)
         elif (into.d != d or into.chains_per_target != m or into.second_moment != full or tuple(into.acc.shape) != (n // m, rows)
               or tuple(into.chain_sum.shape) != (d, n)):
             raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
+        elif log_prob and into.lp_acc is None:
+            raise ValueError("into= was begun without log_prob: its draws so far were not evaluated, so it cannot take log_prob up")
+        log_prob = into.lp_acc is not None
         rest = int(n_samples) - 1
         window = max(1, (256 << 20) // (8 * d * n)) if window is None else int(window)
         if window < 1:
@@ -662,8 +681,17 @@ class RejectionSphericalSliceSampler:
         if burnin:
             self.advance(burnin)
 
+        lp_buf = torch.empty((window, n), dtype=torch.float64, device=self._tdev) if log_prob else None
+
         def fold(x):
             diagnostics.target_moments(x, m, second_moment=full, acc=into.acc, chain_sum=into.chain_sum)
+            if log_prob:
+                x, w = x.contiguous(), int(x.shape[0])
+                with torch.cuda.device(self.device):
+                    _lib.check(self._lib.gsss_batch_logprob_draws(self._target_dev.handle, x.data_ptr(), w, n, self.chain_offset // m,
+                                                                  lp_buf.data_ptr(), current_stream_ptr(self.device)))
+                diagnostics.scalar_moments(lp_buf[:w], m, acc=into.lp_acc, chain_sum=into.lp_chain_sum)
+                into.update_best(lp_buf[:w], x)
 
         fold(self._state[None])                       # draw 0: the state itself is a (1, d, n) window
         buf = torch.empty((window, d, n), dtype=torch.float64, device=self._tdev) if rest else None

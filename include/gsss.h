@@ -260,7 +260,8 @@ int gsss_target_create_mixture(const gsss_target_desc *components, int32_t n_com
  * maximum over the members.  GSSS_E_UNSUPPORTED (gsss_last_error says which): another kind than the two above, members of
  * different kind, d, K or b-ness; from gsss_run: another sampler, replay_dev, rng_state_dev, stats_dev, a chain_offset or n_chains
  * that is no multiple of m or reaches past the last target, a shape without a batch fast kernel in GSSS_MODE_FAST; from
- * gsss_logprob / gsss_gradient always (evaluate the members' own handles).  gsss_kernel_name names the batch builds
+ * gsss_logprob / gsss_gradient always (evaluate the members' own handles, or all of them with gsss_batch_logprob /
+ * gsss_batch_gradient).  gsss_kernel_name names the batch builds
  * ("run_kernel<lane3, VmfMixture, batch>", "screened_kernel<5, ScreenBingham<5>, batch>", ...). */
 int gsss_target_create_batch(const gsss_target_desc *targets, int32_t n_targets, int64_t chains_per_target, int device,
                              gsss_target **out);
@@ -337,6 +338,32 @@ int64_t gsss_stats_rows(int32_t d, int32_t n_modes, int32_t n_lags, int32_t flag
 int64_t gsss_moments_rows(int32_t d, int32_t flags);
 int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_chains, int32_t d, int64_t samples_chain_rows,
                         int64_t chains_per_target, int32_t flags, double *acc_dev, double *chain_sum_dev, int device, void *stream);
+
+/* Distribution.log_prob / .gradient of EVERY member of a gsss_target_create_batch handle in one launch (the batch counterpart of
+ * gsss_logprob / gsss_gradient, which keep refusing a batch).  x_dev is row-major [M][n_per_target][d]: member t evaluates its own
+ * rows, out_dev [M][n_per_target], grad_dev [M][n_per_target][d].  A workgroup serves one target, in the vector layout and with
+ * the target policy gsss_logprob uses for the shape, so every value is the member's own gsss_logprob / gsss_gradient value bit for
+ * bit (a batch that mixes diagonal and dense Bingham members included: these kernels do not read the flag).  n_per_target = 0
+ * does nothing.  GSSS_E_INVALID: a NULL handle, a negative count, NULL pointers with n_per_target > 0; GSSS_E_UNSUPPORTED: a handle
+ * that is no batch, more workgroups (M x ceil(n_per_target / points per workgroup)) than a grid holds -- all before the device
+ * is touched.  The reference evaluates pdf.log_prob(samples) per target on the host. */
+int gsss_batch_logprob(const gsss_target *t, const double *x_dev, int64_t n_per_target, double *out_dev, void *stream);
+int gsss_batch_gradient(const gsss_target *t, const double *x_dev, int64_t n_per_target, double *grad_dev, void *stream);
+/* The same values for a block of draws where gsss_run left it: samples_dev is component-major [n_rows][d][n_chains], chain 0 of
+ * the block being the first chain of target `target0` of the handle; m = the handle's chains_per_target, so the block covers the
+ * targets target0 .. target0 + n_chains / m - 1 and chain c belongs to target target0 + c / m.  out_dev [n_rows][n_chains].
+ * GSSS_E_INVALID: a NULL handle, negative counts, n_chains no multiple of m, a target range that reaches past the last member,
+ * NULL pointers with a non-empty block; GSSS_E_UNSUPPORTED as above.  An empty block does nothing. */
+int gsss_batch_logprob_draws(const gsss_target *t, const double *samples_dev, int64_t n_rows, int64_t n_chains, int64_t target0,
+                             double *out_dev, void *stream);
+/* gsss_target_moments for ONE scalar per draw (the log-density trace): values_dev [n_rows][n_chains], target t owning the chains
+ * [t m, (t + 1) m), m = chains_per_target.  acc_dev [n_chains / m][3], ADDED to: count of draws, sum v, sum v^2; chain_sum_dev NULL
+ * or [n_chains], ADDED to: every chain's sum of its rows.  The same kernels, the same fixed summation order and no atomics: a
+ * call gives the same bits every time.  (gsss_target_moments itself keeps refusing d < 2: a point on a sphere has two
+ * coordinates at least.)  GSSS_E_INVALID: negative counts, m < 1, n_chains no multiple of m, a NULL values_dev / acc_dev with a
+ * non-empty block -- before the device is touched.  n_rows = 0 or n_chains = 0 does nothing. */
+int gsss_scalar_moments(const double *values_dev, int64_t n_rows, int64_t n_chains, int64_t chains_per_target, double *acc_dev,
+                        double *chain_sum_dev, int device, void *stream);
 
 /* 1 if gsss_run accepts `mode` for this target's shape (fast mode is built for the shapes listed in
  * geosss_amd/csrc/gsss_fast_*.hip), else 0. */
