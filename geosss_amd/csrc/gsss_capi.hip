@@ -70,6 +70,41 @@ int64_t resident_workgroups(const void *kern, size_t lds_bytes, int *per_cu_out)
     return (int64_t)per_cu * cus;
 }
 
+const Piece *piece_table_staged(int64_t n_chunks, int64_t resident, int64_t n_steps, int64_t *count_out, int64_t *split_out)
+{
+    struct Entry {
+        int64_t n_chunks, resident, n_steps, count, split;
+        Piece *table;
+    };
+    // (page-locked memory is visible to every device; an entry is never written again or freed, so a copy queued from it on any
+    // stream stays valid.  A process plans a handful of shapes; past kMaxTables of them the launch falls back to one workgroup
+    // per chunk rather than let the cache grow without bound.)
+    constexpr size_t kMaxTables = 256;
+    static std::mutex mu;
+    static std::vector<Entry> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Entry &e : cache)
+        if (e.n_chunks == n_chunks && e.resident == resident && e.n_steps == n_steps) {
+            *count_out = e.count;
+            *split_out = e.split;
+            return e.table;
+        }
+    if (cache.size() >= kMaxTables) return nullptr;
+    int64_t split = 0;
+    const std::vector<Piece> table = piece_plan(n_chunks, resident, n_steps, &split);
+    if (table.empty()) return nullptr;
+    void *host = nullptr;
+    if (hipHostMalloc(&host, table.size() * sizeof(Piece), hipHostMallocPortable) != hipSuccess || host == nullptr) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    memcpy(host, table.data(), table.size() * sizeof(Piece));
+    cache.push_back(Entry{n_chunks, resident, n_steps, (int64_t)table.size(), split, static_cast<Piece *>(host)});
+    *count_out = (int64_t)table.size();
+    *split_out = split;
+    return cache.back().table;
+}
+
 void slice_fallback_note(const char *why)
 {
     if (getenv("GSSS_DEBUG_OCCUPANCY")) fprintf(stderr, "gsss: %s\n", why);
@@ -1267,6 +1302,24 @@ int gsss_batch_plan(int32_t kind, int32_t d, int32_t k, int32_t has_b, int64_t n
     if (grid) *grid = bp.grid;
     if (lane_use) *lane_use = bp.lane_use;
     return GSSS_OK;
+}
+
+int64_t gsss_piece_plan(int64_t n_chunks, int64_t resident, int64_t n_steps, int32_t *table_out, int64_t capacity)
+{
+    if (n_chunks < 1 || resident < 1 || n_steps < 1 || capacity < 0) {
+        set_error("gsss_piece_plan: need n_chunks, resident, n_steps >= 1 and capacity >= 0 (%lld, %lld, %lld, %lld)", (long long)n_chunks,
+                  (long long)resident, (long long)n_steps, (long long)capacity);
+        return GSSS_E_INVALID;
+    }
+    const std::vector<Piece> table = piece_plan(n_chunks, resident, n_steps);
+    if (table_out != nullptr) {
+        if ((int64_t)table.size() > capacity) {
+            set_error("gsss_piece_plan: the table has %lld pieces, the buffer holds %lld", (long long)table.size(), (long long)capacity);
+            return GSSS_E_INVALID;
+        }
+        if (!table.empty()) memcpy(table_out, table.data(), table.size() * sizeof(Piece));
+    }
+    return (int64_t)table.size();
 }
 
 int gsss_last_launch(int64_t *grid_out, int32_t *slice_steps_out, double *sliced_fraction_out)

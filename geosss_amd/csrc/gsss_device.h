@@ -12,6 +12,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "../../include/gsss.h"
 #include "gsss_math.h"
 
@@ -64,7 +67,8 @@ struct RunBlock {
     // state travels from slice to slice through HBM (SliceSched below): the dispatcher refills a slot whenever a slice ends, and
     // the chip drains for one slice, not for a whole chunk.  Zeroed workspace: [0] ticket | [2 ..) progress[n_chunks] | dead[n_chains].
     uint32_t *sched;
-    int32_t slice_steps;       // steps per slice; boundaries sit at multiples of it in GLOBAL step ids
+    int32_t slice_steps;       // steps per slice; boundaries sit at multiples of it in GLOBAL step ids.  0 with sched set: the launch
+                               // follows a piece table behind dead[] (piece_plan, SliceSched::take_piece; the lane kernels only)
     int32_t sched_first;       // chunks below this one are not sliced: their workgroups (blockIdx < sched_first) run the whole launch
                                // (the lane kernels slice only the last, partial round of their workgroups)
 };
@@ -112,6 +116,8 @@ __device__ __forceinline__ const T &first_of(const T &x)
 // runs up to the next one), a multiple of kCoefRefresh, so a kernel that refreshes carried quantities at those steps computes
 // the same bits sliced or not.  A wait that does not end (cannot happen) gives up after ~4 s per predecessor and flags the chains.
 // ------------------------------------------------------------------------------------------
+// what an entry of a piece table is (piece_plan below)
+enum PieceKind : int32_t { kPieceWhole = 0, kPieceHead = 1, kPieceTail = 2 };
 struct SliceSched {
     // (no state of its own: everything follows from the launch arguments, so that nothing of it stays in registers while a
     // slice runs -- the kernels that use it have no scalar register to spare)
@@ -159,6 +165,57 @@ struct SliceSched {
                 // publishes its progress like any other, so its successors do not wait out limits of their own: ADVICE r4)
                 const uint64_t limit = (uint64_t)(slice + 1u < 8u ? slice + 1u : 8u) << 22;
                 while (__hip_atomic_load(progress(a) + chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < slice) {
+                    __builtin_amdgcn_s_sleep(32);
+                    if (++spins > limit) {
+                        ok = 0;
+                        break;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                *word = ok;
+            }
+            __syncthreads();
+            timed_out = __builtin_amdgcn_readfirstlane((int)*word) == 0;
+        }
+        return true;
+    }
+    // The table form (piece_plan below; the lane kernels): the workgroup that draws ticket t runs entry t of the launch's piece
+    // table -- a whole chunk (`kind` kPieceWhole: an unsliced workgroup, plain stores, no flags), the head [0, b) of a split chunk
+    // (hands over and publishes like a slice 0) or its tail [b, n_steps) (waits for the head like a slice 1: same acquire, same
+    // give-up limit that ends in error flags).  Progress: a tail waits only for a head, a head waits for nothing, and the head
+    // of a chunk stands before its tail in the table, so it drew the earlier ticket -- it is resident or done whatever the
+    // dispatcher does, even when fewer workgroups are resident than the plan assumed.  The wait always ends.
+    // The table starts at the first 16-byte boundary behind dead[]; the grid is its length.
+    __device__ static __forceinline__ const uint32_t *pieces(const RunBlock &a, int per_block)
+    {
+        const size_t words = 2 + (size_t)chunks(a, per_block) + (size_t)a.n_chains;
+        return a.sched + ((words + 3) & ~(size_t)3);
+    }
+    __device__ static __forceinline__ bool take_piece(const RunBlock &a, int per_block, uint32_t *word, uint32_t &chunk, int32_t &s_begin,
+                                                      int32_t &len, int32_t &kind, bool &timed_out)
+    {
+        if (threadIdx.x == 0) *word = __hip_atomic_fetch_add(a.sched, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)*word);
+        if (t >= gridDim.x) return false;
+        const uint32_t *e = pieces(a, per_block) + 4 * (size_t)t;  // (written by the launch's copy, before the kernel: plain loads)
+        chunk = e[0];
+        s_begin = (int32_t)e[1];
+        len = (int32_t)e[2];
+        kind = (int32_t)e[3];
+        if (threadIdx.x == 0) {
+            word[1] = chunk;
+            word[2] = 0u;  // publish(): progress[chunk] = 1, the head has been handed over
+        }
+        timed_out = false;
+        if (kind == kPieceTail) {
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                uint32_t ok = 1;
+                uint64_t spins = 0;
+                const uint64_t limit = (uint64_t)2u << 22;  // (slice 1's in take() above)
+                while (__hip_atomic_load(progress(a) + chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 1u) {
                     __builtin_amdgcn_s_sleep(32);
                     if (++spins > limit) {
                         ok = 0;
@@ -301,11 +358,106 @@ inline SlicePlan plan_slices(Kern kern, size_t lds_bytes, const RunBlock &rb, in
     return p;
 }
 
-// The lane kernels (two chains per lane, a workgroup's unit of time is a lane's pair of chains) slice only their LAST, PARTIAL
-// round of workgroups, and only when it is small: n_chunks = k resident + rem with rem <= 3/4 resident -- the first k resident
-// workgroups run the whole launch as ever (blockIdx < first), the rem chunks behind them are cut into slices that fill the
-// chip when the full rounds end.  (A slice of a lane kernel ends when its slowest lane does: ~10 % of lane tail at 128 steps,
-// paid on the partial round only.  At 10^6 chains: K = 10 mixture and compact Bingham 2.54 rounds of 768 -> sliced; headline 1.53 rounds of 1280 -> sliced.)
+// ------------------------------------------------------------------------------------------
+// The piece plan of the lane kernels' partial round (host side, a pure function).  C chunks of N steps on
+// R resident workgroups, C > R and not a multiple of it: uniform slices (plan_partial_round below) run the last, partial round
+// at half occupancy or less.  Here every resident slot gets the same amount of work and a chunk is split at most once --
+// McNaughton's wrap-around rule: lay the chunks end to end, C N steps, and cut the line into R slots of T = ceil(C N / R)
+// steps.  T >= N, so a chunk meets at most one boundary.  A chunk that straddles slots j and j + 1 runs as two pieces: the part
+// at the START of slot j + 1 is its head, steps [0, b); the part at the END of slot j is its tail, steps [b, N) -- the head is
+// planned to end T - N steps before the tail begins.  Boundaries are moved down by less than kPieceMin steps so that neither
+// part is shorter than kPieceMin (a chunk within kPieceMin of a boundary stays whole; slots then differ by < kPieceMin steps).
+// The table lists the pieces by planned start within their slot, ties by slot: ticket t takes entry t (SliceSched::take_piece),
+// so with workgroups started in ticket order, each on the slot that falls free first, the launch follows the plan.  A head
+// starts at 0 and a tail later, so a head precedes its tail in the table.  The plan does not depend on step_offset: the lane
+// kernels carry nothing across steps but the chain itself.
+// ------------------------------------------------------------------------------------------
+constexpr int32_t kPieceMin = 32;
+constexpr int64_t kPieceMinSteps = 256;  // launches shorter than this are not cut (as for the uniform slices: two of 128 steps)
+struct Piece {
+    int32_t chunk, s_begin, len, kind;
+};
+static_assert(sizeof(Piece) == 16, "a table entry is four words");
+inline bool piece_plan_applies(int64_t n_chunks, int64_t resident, int64_t n_steps)
+{
+    return resident >= 1 && n_chunks > resident && n_chunks % resident != 0 && n_steps >= kPieceMinSteps && n_steps < 0x40000000ll &&
+           n_chunks < 0x40000000ll;
+}
+// the table (empty: no plan for this shape); split_out: the chunks that run as head and tail
+inline std::vector<Piece> piece_plan(int64_t n_chunks, int64_t resident, int64_t n_steps, int64_t *split_out = nullptr)
+{
+    std::vector<Piece> table;
+    if (split_out) *split_out = 0;
+    if (!piece_plan_applies(n_chunks, resident, n_steps)) return table;
+    const int64_t C = n_chunks, R = resident, N = n_steps, W = C * N;  // (< 2^60)
+    struct Planned {
+        int64_t start, slot;
+        Piece piece;
+    };
+    std::vector<Planned> planned;
+    planned.reserve((size_t)(C + R));
+    int64_t lo = 0, split = 0;
+    for (int64_t j = 0; j < R; ++j) {
+        int64_t hi = W;
+        if (j + 1 < R) {
+            hi = (j + 1) * (W / R) + (j + 1) * (W % R) / R;  // floor((j + 1) W / R), the ideal boundary: slots of T or T - 1 steps
+            const int64_t x = hi % N;
+            if (x < kPieceMin)
+                hi -= x;  // the chunk stays whole, in the next slot
+            else if (N - x < kPieceMin)
+                hi -= kPieceMin - (N - x);  // its head is kPieceMin steps
+            // a chunk is split at most once: not before the end of the chunk that the previous boundary cut
+            const int64_t pc = lo / N, px = lo % N;
+            const int64_t floor_pos = px ? (pc + 1) * N : lo;
+            if (hi < floor_pos) hi = floor_pos;
+            // a slot of one head (N - px steps) and one tail (x steps): the tail begins when the head of ITS chunk, N - x steps at the
+            // start of the next slot, has ended
+            if (px && hi / N == pc + 1 && hi % N != 0 && hi % N < px) hi = (pc + 1) * N + px;
+        }
+        for (int64_t p = lo; p < hi;) {
+            const int64_t c = p / N, x = p % N;
+            const int64_t end = (c + 1) * N < hi ? (c + 1) * N : hi;
+            Piece e;
+            e.chunk = (int32_t)c;
+            if (x) {  // the part of chunk c at the start of the slot: its head
+                e.s_begin = 0, e.len = (int32_t)(N - x), e.kind = kPieceHead;
+            } else if (end - p < N) {  // the part at the end of the slot: its tail
+                e.s_begin = (int32_t)(N - (end - p)), e.len = (int32_t)(end - p), e.kind = kPieceTail;
+                ++split;
+            } else {
+                e.s_begin = 0, e.len = (int32_t)N, e.kind = kPieceWhole;
+            }
+            planned.push_back(Planned{p - lo, j, e});
+            p = end;
+        }
+        lo = hi;
+    }
+    std::stable_sort(planned.begin(), planned.end(), [](const Planned &a, const Planned &b) { return a.start != b.start ? a.start < b.start : a.slot < b.slot; });
+    table.reserve(planned.size());
+    for (const Planned &p : planned) table.push_back(p.piece);
+    if (split_out) *split_out = split;
+    return table;
+}
+
+// The launch's copy of a table: page-locked, built once per (chunks, resident, steps) and kept for the life of the process
+// (gsss_capi.hip), so that a launch uploads it in stream order without waiting for anything.  NULL: no plan, or no memory.
+const Piece *piece_table_staged(int64_t n_chunks, int64_t resident, int64_t n_steps, int64_t *count_out, int64_t *split_out);
+constexpr bool kPiecePlanDefault = true;  // GSSS_PIECE_PLAN in the environment overrides it ("0": uniform slices of 128 steps)
+constexpr size_t piece_table_offset(int64_t n_chunks, int64_t n_chains) { return (slice_sched_bytes(n_chunks, n_chains) + 15) / 16 * 16; }
+
+// The lane kernels (two chains per lane, a workgroup's unit of time is a lane's pair of chains) never slice their full rounds of
+// workgroups.  What they do about the last, partial one:
+//   GSSS_SLICE_STEPS unset   the piece plan above: every workgroup of the launch draws a ticket and runs its entry of the table,
+//                            which travels in the launch's workspace behind dead[] (uploaded in stream order from a page-locked
+//                            copy; no host synchronisation).  Reported (gsss_last_launch): grid = pieces, sliced_fraction = split
+//                            chunks / chunks, slice_steps = ceil(n_steps / 2) -- each split chunk hands over once, which is what
+//                            that slice length prices.  GSSS_PIECE_PLAN=0: the uniform slices below, 128 steps (A/B).
+//   GSSS_SLICE_STEPS=N > 0   uniform slices, and only when the partial round is small: n_chunks = k resident + rem with
+//                            rem <= 3/4 resident -- the first k resident workgroups run the whole launch as ever (blockIdx < first),
+//                            the rem chunks behind them are cut into slices that fill the chip when the full rounds end.  (A slice
+//                            of a lane kernel ends when its slowest lane does: ~10 % of lane tail at 128 steps.)
+//   GSSS_SLICE_STEPS=0       one workgroup per chunk.
+// A failed allocation falls back to one workgroup per chunk.
 template <class Kern>
 inline SlicePlan plan_partial_round(Kern kern, size_t lds_bytes, const RunBlock &rb, int64_t n_chunks, bool allowed, hipStream_t st,
                                     int32_t &first_out)
@@ -315,6 +467,35 @@ inline SlicePlan plan_partial_round(Kern kern, size_t lds_bytes, const RunBlock 
     first_out = 0;
     last_launch() = LaunchInfo{n_chunks, 0, 0.0};
     if (!allowed) return p;
+    const char *env_pieces = getenv("GSSS_PIECE_PLAN");  // (read per launch: tests switch it)
+    if (getenv("GSSS_SLICE_STEPS") == nullptr && (env_pieces ? env_pieces[0] != '0' : kPiecePlanDefault)) {
+        const int64_t resident = resident_workgroups(reinterpret_cast<const void *>(kern), lds_bytes);
+        if (!piece_plan_applies(n_chunks, resident, rb.n_steps) || rb.n_chains >= 0x7FFFFFFFll) return p;
+        int64_t count = 0, split = 0;
+        const Piece *table = piece_table_staged(n_chunks, resident, rb.n_steps, &count, &split);
+        if (table == nullptr || count < 1) {
+            slice_fallback_note("no page-locked memory for the piece table: launching one workgroup per chunk");
+            return p;
+        }
+        const size_t head_bytes = piece_table_offset(n_chunks, rb.n_chains), bytes = head_bytes + (size_t)count * sizeof(Piece);
+        void *ws = nullptr;
+        if (hipMallocAsync(&ws, bytes, st) != hipSuccess || ws == nullptr) {
+            (void)hipGetLastError();
+            slice_fallback_note("hipMallocAsync of the piece workspace failed: launching one workgroup per chunk");
+            return p;
+        }
+        if (hipMemsetAsync(ws, 0, head_bytes, st) != hipSuccess ||
+            hipMemcpyAsync(static_cast<char *>(ws) + head_bytes, table, (size_t)count * sizeof(Piece), hipMemcpyHostToDevice, st) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFreeAsync(ws, st);
+            return p;
+        }
+        p.ws = static_cast<uint32_t *>(ws);
+        p.grid = count;
+        p.slice_steps = 0;  // (RunBlock::slice_steps 0 with a workspace: the table form)
+        last_launch() = LaunchInfo{count, (int32_t)((rb.n_steps + 1) / 2), (double)split / (double)n_chunks};
+        return p;
+    }
     const int env_steps = slice_length(rb.n_steps);
     if (env_steps <= 0 || rb.n_steps < 2 * (int64_t)env_steps) return p;
     const int64_t resident = resident_workgroups(reinterpret_cast<const void *>(kern), lds_bytes);

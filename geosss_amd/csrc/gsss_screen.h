@@ -859,17 +859,24 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
 
     const int32_t n = (int32_t)a.n_chains;
     // This workgroup's work: its chunk of chains for the whole launch -- or, in the sliced partial round of a launch
-    // (plan_partial_round, gsss_device.h), the (chunk, step slice) of the ticket it draws.  A chain's step count runs over the
-    // launch's steps [s_begin, n_steps): counters of the stream and retained rows need nothing else.
+    // (plan_partial_round, gsss_device.h), the (chunk, step slice) of the ticket it draws -- or, in a launch that follows a piece
+    // table (piece_plan; a.slice_steps == 0), the entry of its ticket: a whole chunk, which it runs as an unsliced workgroup does
+    // (`sliced` false), or the head or tail of a split one.  A chain's step count runs over the launch's steps
+    // [s_begin, n_steps): counters of the stream and retained rows need nothing else.
     constexpr int kChunk = (screen_parks<D, TP>() && !NUMPY && !STAGE && !BATCH) ? 2 * kBlock : kBlock;  // chains per workgroup
     __shared__ uint32_t sched_word[4];
-    const bool sliced = a.sched != nullptr && (int32_t)blockIdx.x >= a.sched_first;
+    bool sliced = a.sched != nullptr && (int32_t)blockIdx.x >= a.sched_first;
     uint32_t chunk = blockIdx.x;
     int32_t s_begin = 0, n_steps = (int32_t)a.n_steps;
     bool timed_out = false;
     if (sliced) {
         int32_t len;
-        if (!SliceSched::take(a, a.one_per_lane ? kBlock : kChunk, sched_word, chunk, s_begin, len, timed_out)) return;  // (one ticket per workgroup: never)
+        if (a.slice_steps == 0) {
+            int32_t kind;
+            if (!SliceSched::take_piece(a, a.one_per_lane ? kBlock : kChunk, sched_word, chunk, s_begin, len, kind, timed_out)) return;  // (one ticket per workgroup: never)
+            sliced = kind != kPieceWhole;
+        } else if (!SliceSched::take(a, a.one_per_lane ? kBlock : kChunk, sched_word, chunk, s_begin, len, timed_out))
+            return;  // (one ticket per workgroup: never)
         n_steps = s_begin + len;
     }
     const bool shrink = a.sampler == GSSS_SHRINK;

@@ -296,10 +296,24 @@ int gsss_run(const gsss_target *t, const gsss_run_args *args, void *stream);
  * launch; same results bit for bit; GSSS_SLICE_STEPS in the environment sets the length, 0 turns it off; a launch is cut into at
  * most 64 slices per chunk -- long launches get longer slices, n_steps = 10^6 -> 15 680 steps --, so the chain of hand-overs a
  * workgroup may wait on stays short for any n_steps < 2^31).  slice_steps 0:
- * unsliced; grid 0: a kernel family that never slices.  sliced_fraction: the share of the chains that ran sliced (the lane
- * kernels slice only a small last round of workgroups).  Any pointer may be NULL.  There is nothing in the reference this
- * replaces. */
+ * unsliced; grid 0: a kernel family that never slices.  sliced_fraction: the share of the chains that ran sliced.
+ * The lane kernels never slice their full rounds of workgroups.  With GSSS_SLICE_STEPS unset they run a launch whose chunks are
+ * no whole number of rounds by a PIECE PLAN (gsss_piece_plan): every resident workgroup slot gets the same number of steps and a
+ * chunk is split at most once, into a head and a tail.  Such a launch reports grid = the number of pieces, sliced_fraction =
+ * split chunks / chunks and slice_steps = ceil(n_steps / 2): each split chunk is handed over once, and that is what this slice
+ * length prices in the formula above.  GSSS_PIECE_PLAN=0, or GSSS_SLICE_STEPS=N > 0, selects uniform slices of a small last
+ * round instead (128 steps, or N), reported as such.  Any pointer may be NULL.  There is nothing in the reference this replaces. */
 int gsss_last_launch(int64_t *grid_out, int32_t *slice_steps_out, double *sliced_fraction_out);
+
+/* The piece plan of a lane-kernel launch of n_chunks chunks of chains x n_steps steps on `resident` workgroup slots: the chunks
+ * laid end to end and cut into `resident` slots of ceil(n_chunks n_steps / resident) steps, boundaries moved by less than 32
+ * steps so that no part of a split chunk is shorter than 32.  table_out: NULL or `capacity` entries of four int32 -- chunk, first
+ * step, steps, kind (0 a whole chunk; 1 the head [0, b) of a split chunk, at the start of a slot; 2 its tail [b, n_steps), at the
+ * end of the slot before) -- in the order workgroups take them: by planned start within the slot, ties by slot, a head always
+ * before its tail.  Returns the number of pieces; 0: no plan (n_chunks <= resident, a whole number of rounds, or n_steps < 256);
+ * GSSS_E_INVALID for arguments < 1 or a table that does not fit the buffer.  A pure host function: no device is needed.  There
+ * is nothing in the reference this replaces. */
+int64_t gsss_piece_plan(int64_t n_chunks, int64_t resident, int64_t n_steps, int32_t *table_out, int64_t capacity);
 
 /* The fast-mode launch plan of a batch of n_targets members (kind, d, k, has_b) with m chains each: chains a workgroup takes, the
  * most targets it stages, the grid, and lanes that carry a chain / lanes launched (chains / (grid x chains a workgroup takes)).
