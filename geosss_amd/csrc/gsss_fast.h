@@ -67,7 +67,7 @@ struct FastVmf {
         }
     };
     static constexpr int kCoefWords = 2 * KC + 1;
-    __host__ __device__ static size_t lds_doubles() { return (size_t)KC * D + KC; }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)KC * D + KC; }
     int K;  // components of the target, K <= KC: the kernels are built for KC, the surplus ones are padded with
             // mu = 0, logc = log(0), so that they add exactly +0.0 to every sum (a mixture of any K <= KC runs the KC kernel)
     __device__ void stage(double *lds, const TargetBlock &tb)
@@ -179,7 +179,7 @@ struct FastBingham {
         }
     };
     static constexpr int kCoefWords = 5;
-    __host__ __device__ static size_t lds_doubles() { return (size_t)D * D + D; }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)D * D + D; }
     bool diagonal;  // A is diagonal (the eigenbasis targets of scripts/bingham.py:131): O(d) coefficients
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
@@ -272,7 +272,7 @@ struct FastCurve {
         }
     };
     static constexpr int kCoefWords = 2 * NK;
-    __host__ __device__ static size_t lds_doubles() { return (size_t)NK * D + 4 * (size_t)(NK - 1); }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)NK * D + 4 * (size_t)(NK - 1); }
     int nseg;  // segments of the target's curve: k - 1 <= NK - 1 (a curve of fewer knots runs the NK kernel: the surplus
                // knot rows are zeros and their segments never take part in the maximum)
     __device__ void stage(double *lds, const TargetBlock &tb)
@@ -400,7 +400,7 @@ struct FastMixture {
         }
     };
     static constexpr int kCoefWords = 5 * KC + 1;
-    __host__ __device__ static size_t lds_doubles() { return (size_t)KC * kTermDoubles; }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)KC * kTermDoubles; }
     int K;          // terms in use
     uint32_t quad;  // bit k: term k is a Bingham term
     // term k of the blob (gsss_device.h, Mixture): component c, and the inner index j of a vMF component
@@ -1024,7 +1024,7 @@ struct CoopCurve {
     static constexpr int kScratchPerGroup = 0;
     Scalar sc;
     const double *rows;  // LDS [NK][DPAD]
-    __host__ __device__ static size_t lds_doubles() { return (size_t)NK * V::DPAD + 4 * (size_t)(NK - 1); }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)NK * V::DPAD + 4 * (size_t)(NK - 1); }
     int nseg;  // k - 1 segments, k <= NK knots (surplus rows zero, surplus segments out of the maximum)
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
@@ -1128,7 +1128,7 @@ struct CoopVmf {
     __device__ __forceinline__ double level_distributed(const Mine &, int, double, double) const { return 0.0; }
     Scalar sc;
     const double *rows;  // LDS [KC][DPAD]
-    __host__ __device__ static size_t lds_doubles() { return (size_t)KC * V::DPAD + KC; }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)KC * V::DPAD + KC; }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         // K = tb.k <= KC components; the surplus rows are zeros with logc = log 0 (exact zeros in every sum)

@@ -102,6 +102,37 @@ struct ScreenVmf : FastVmf<D, KC> {
     // from the counter-based stream -- which makes the parked state 15 words: five workgroups per CU instead of four (the
     // kernel needs 95 registers: five wavefronts per SIMD fit)
     static constexpr bool kRegenThr = D == 3 && KC <= 3;
+    // The screen's set-up in LOG2 UNITS: the plain builds of the kernel (everything but the batch builds, whose LDS is planned
+    // by gsss_fast_select.h from lds_doubles()) stage a second copy of the rows multiplied by L = log2 e once per workgroup --
+    // mu_k L and logc_k L behind the unscaled rows -- and setup32_log2() forms the single-precision pack from it: no product
+    // by L per coefficient and step (3 K v_mul_f64).  Only where the copy's K (D + 1) doubles change neither the resident
+    // workgroups nor a pick of fast_select: S^2, K <= 3 -- 31 872 -> 31 968 B per workgroup, 25 allocation granules of 1280 B
+    // either way, five workgroups per CU.  (Wider shapes: unchecked, they keep make32.)  The double-precision consumers --
+    // coeffs(), decide(), threshold(), level_exact(), fast_kernel -- read the unscaled rows as before.
+    static constexpr bool kLog2Rows = D == 3 && KC <= 3;
+    static_assert(!kLog2Rows || kParkSkip == 0, "refill() would have to form its floats from the scaled rows too");
+    __host__ __device__ static constexpr size_t log2_doubles() { return kLog2Rows ? (size_t)KC * D + KC : 0; }
+    // stage() followed by the scaled copy, formed from the rows AS STAGED (zero rows, kLogZero, -inf clamped: stage()'s rules,
+    // stated there alone), each times L
+    __device__ void stage_log2(double *lds, const TargetBlock &tb)
+    {
+        constexpr double L = 1.4426950408889634074;
+        Base::stage(lds, tb);
+        __syncthreads();
+        const int rows = (int)Base::lds_doubles();
+        for (int i = threadIdx.x; i < rows; i += kBlock) lds[rows + i] = lds[i] * L;
+    }
+    // mu_k . x and mu_k . u over the rows at `rows` (the staged ones, or their copy in log2 units)
+    __device__ __forceinline__ static void dots(const double *rows, int k, const double (&x)[D], const double (&u)[D], double &ax, double &au)
+    {
+        ax = 0.0, au = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const double mkj = rows[k * D + j];
+            ax = fma(mkj, x[j], ax);
+            au = fma(mkj, u[j], au);
+        }
+    }
     __device__ __forceinline__ void retail(float (&)[kCoef32Floats]) const {}
     __device__ __forceinline__ void refill(const double (&x)[D], const double (&u)[D], float (&q)[kCoef32Floats]) const
     {
@@ -123,17 +154,7 @@ struct ScreenVmf : FastVmf<D, KC> {
     __device__ __forceinline__ void coeffs(Coef &cf, const double (&x)[D], const double (&u)[D]) const
     {
 #pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            double ax = 0.0, au = 0.0;
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const double mkj = this->mu[k * D + j];
-                ax = fma(mkj, x[j], ax);
-                au = fma(mkj, u[j], au);
-            }
-            cf.ax[k] = ax;
-            cf.au[k] = au;
-        }
+        for (int k = 0; k < KC; ++k) dots(this->mu, k, x, u, cf.ax[k], cf.au[k]);
         double m = -INFINITY;  // the offset make() chose for this step
 #pragma unroll
         for (int k = 0; k < KC; ++k) m = fmax(m, cf.ax[k] + this->logc[k]);
@@ -144,10 +165,15 @@ struct ScreenVmf : FastVmf<D, KC> {
     // log2 thr itself is only formed in single precision here (its error is part of the margin); the double-
     // precision threshold is formed when a try is left undecided (threshold()).  Returns false when the level of
     // x is not a positive finite number.
+    // The margin counts SINGLE-precision roundings: one per coefficient of q (the conversion), those of a try's fused
+    // multiply-adds and those of log2 thr.  setup32_log2() (kLog2Rows) forms the same three coefficients from the rows scaled by
+    // L beforehand: one double-precision rounding LESS per coefficient (no product by L; the scaled rows' own roundings are
+    // double-precision ones like those of the sums, far below the 2^-24 counted) and the same single-precision ones, and b is
+    // taken from the q it formed -- the bound on b and the margin formula hold for it as written.
     __device__ __forceinline__ bool make32(const Coef &cf, double u_thr, float (&q)[kCoef32Floats]) const
     {
         constexpr double L = 1.4426950408889634074;
-        float b = 0.0f, s0 = 0.0f;
+        float s0 = 0.0f;
 #pragma unroll
         for (int k = 0; k < KC; ++k) {
             q[k] = (float)(cf.ax[k] * L);
@@ -155,6 +181,12 @@ struct ScreenVmf : FastVmf<D, KC> {
             q[2 * KC + k] = (float)((this->logc[k] - cf.m) * L);
             s0 += __builtin_amdgcn_exp2f(q[k] + q[2 * KC + k]);  // theta = 0: cos = 1, sin = 0 exactly
         }
+        return finish32(u_thr, q, s0);
+    }
+    // from the rounded coefficients and s0, the single-precision level of x over 2^m, on: log2 thr, b and the margin
+    __device__ __forceinline__ bool finish32(double u_thr, float (&q)[kCoef32Floats], float s0) const
+    {
+        float b = 0.0f;
         // log2(level(x) U): s0 lies in [1, K] (the largest exponent is 0 up to rounding)
         int e;
         const float m0 = frexpf(s0, &e);
@@ -224,6 +256,28 @@ struct ScreenVmf : FastVmf<D, KC> {
         coeffs(cf, x, u);
         return make32(cf, u_thr, q);
     }
+    // setup32 from the rows staged in log2 units (stage_log2): ax' = (mu L) . x, au' = (mu L) . u by coeffs()'s dots()
+    // over the scaled rows, m' = max_k (ax'_k + lc'_k), and the pack is their conversion -- nothing of it enters a chain
+    __device__ __forceinline__ bool setup32_log2(const double (&x)[D], const double (&u)[D], double u_thr, float (&q)[kCoef32Floats]) const
+    {
+        const double *mul = this->mu + Base::lds_doubles(), *lcl = this->logc + Base::lds_doubles();
+        double m = -INFINITY;
+        float s0 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            double ax, au;
+            dots(mul, k, x, u, ax, au);
+            q[k] = (float)ax;
+            q[KC + k] = (float)au;
+            m = fmax(m, ax + lcl[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            q[2 * KC + k] = (float)(lcl[k] - m);
+            s0 += __builtin_amdgcn_exp2f(q[k] + q[2 * KC + k]);  // as make32 forms it
+        }
+        return finish32(u_thr, q, s0);
+    }
     __device__ __forceinline__ bool decide(const double (&x)[D], const double (&u)[D], double u_thr, double c, double s) const
     {
         Coef cf;
@@ -231,6 +285,21 @@ struct ScreenVmf : FastVmf<D, KC> {
         return level_exact(cf, c, s) > thr;
     }
 };
+
+// whether a build of screened_kernel stages and uses the rows in log2 units (ScreenVmf::kLog2Rows; never the batch builds)
+template <class TP, class = void>
+struct screen_log2_rows : std::false_type {};
+template <class TP>
+struct screen_log2_rows<TP, std::enable_if_t<TP::kLog2Rows>> : std::true_type {};
+// doubles of LDS in front of the draw tables in the plain builds: the target's rows and, where staged, their log2 copy
+template <class TP>
+__host__ __device__ constexpr size_t screen_row_doubles()
+{
+    if constexpr (screen_log2_rows<TP>::value)
+        return TP::lds_doubles() + TP::log2_doubles();
+    else
+        return TP::lds_doubles();
+}
 
 // Bingham / BinghamFisher: log-density q(theta) = c^2 qxx + c s qxu + s^2 quu + c bx + s bu (distributions.py:86, :113-114),
 // accepted iff q(theta) > thr = q(0) + log U.  With c^2 + s^2 = 1 the threshold is folded into the quadratic terms, so the
@@ -326,7 +395,7 @@ struct ScreenBinghamDiag {
     struct Coef {
         double qxx, qxu, quu;
     };
-    __host__ __device__ static size_t lds_doubles() { return (size_t)D; }
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)D; }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         for (int i = threadIdx.x; i < D; i += kBlock) lds[i] = tb.blob[(size_t)i * D + i];
@@ -618,7 +687,7 @@ struct ScreenCurve : FastCurve<D, NK> {
     __device__ __forceinline__ void retail(float (&)[kCoef32Floats]) const {}
     __device__ __forceinline__ void refill(const double (&)[D], const double (&)[D], float (&)[kCoef32Floats]) const {}
     Curve32<NK> c32;
-    __host__ __device__ static size_t lds_doubles() { return Base::lds_doubles() + 2 * (size_t)(NK - 1); }
+    __host__ __device__ static constexpr size_t lds_doubles() { return Base::lds_doubles() + 2 * (size_t)(NK - 1); }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         Base::stage(lds, tb);
@@ -737,7 +806,7 @@ __host__ __device__ constexpr bool screen_parks()
 template <int D, class TP, bool REPLAY>
 __host__ __device__ constexpr size_t screen_lds_doubles()
 {
-    return TP::lds_doubles() + kTabLds + (screen_parks<D, TP>() ? (size_t)(REPLAY ? ScreenChain<D, TP>::kWords
+    return screen_row_doubles<TP>() + kTabLds + (screen_parks<D, TP>() ? (size_t)(REPLAY ? ScreenChain<D, TP>::kWords
                                                                         : ScreenChain<D, TP>::kWordsNoReplay) * kBlock
                                                       : 0);
 }
@@ -834,17 +903,22 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     extern __shared__ __attribute__((aligned(16))) double lds[];
     TP tp;
     constexpr bool kShared = kIsBatchShared<BB...>;  // (BatchShared in BatchBlock's place: stage_shared, gsss_fast.h)
+    constexpr bool kLog2 = !BATCH && screen_log2_rows<TP>::value;  // the rows once more in log2 units, behind the unscaled ones
+    constexpr size_t kRows = BATCH ? TP::lds_doubles() : screen_row_doubles<TP>();
     [[maybe_unused]] int32_t shared_id = 0;
     if constexpr (kShared) {
         shared_id = stage_shared(tp, lds, tb, first_of(batch...), (int32_t)a.n_chains);
     } else {
         if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
-        tp.stage(lds, tb);
+        if constexpr (kLog2)
+            tp.stage_log2(lds, tb);
+        else
+            tp.stage(lds, tb);
     }
-    const fm::Tables tab = stage_tables(kShared ? lds : lds + TP::lds_doubles());
-    unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + TP::lds_doubles() + kTabLds) + threadIdx.x;
+    const fm::Tables tab = stage_tables(kShared ? lds : lds + kRows);
+    unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + kRows + kTabLds) + threadIdx.x;
     NumpyDraws<V> nd;
-    if constexpr (NUMPY) nd.stage(lds + TP::lds_doubles() + kTabLds);
+    if constexpr (NUMPY) nd.stage(lds + kRows + kTabLds);
     // Retained rows in the reference's (chains, draws, dims) order are 8 D bytes at an 8 D byte stride: for D not a multiple of
     // four a row ends inside a 32-byte sector, and rows that leave one at a time (a chain keeps a row every `thin` steps,
     // milliseconds apart) are written as partial sectors -- 1.39 x the bytes at D = 10.  With one chain per lane the LDS that
@@ -1012,7 +1086,11 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
             for (int j = 0; j < D; ++j) cur.u[j] *= rnw;
         }
         cur.thr = u_thr;  // the uniform; the double-precision threshold is formed only if a try stays undecided
-        const bool finite = tp.setup32(cur.x, cur.u, u_thr, reinterpret_cast<float (&)[TP::kCoef32Floats]>(cur.q));
+        bool finite;
+        if constexpr (kLog2)
+            finite = tp.setup32_log2(cur.x, cur.u, u_thr, reinterpret_cast<float (&)[TP::kCoef32Floats]>(cur.q));
+        else
+            finite = tp.setup32(cur.x, cur.u, u_thr, reinterpret_cast<float (&)[TP::kCoef32Floats]>(cur.q));
         // verification (GSSS_VARIANT_FAST_VERIFY): an infinite margin leaves EVERY try undecided -- each is then decided in double
         // precision by decide(), and the run must reproduce the screened one bit for bit
         // (built into the kernels of d = 11 .. 16, which have no all-double lane sibling to be compared with; d <= 10 is held to
@@ -1370,7 +1448,7 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
 template <int D, class TP>
 int do_screened_numpy(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 {
-    const size_t lds = (TP::lds_doubles() + kTabLds + NumpyDraws<LaneVec<D>>::kLdsDoubles) * sizeof(double);
+    const size_t lds = (screen_row_doubles<TP>() + kTabLds + NumpyDraws<LaneVec<D>>::kLdsDoubles) * sizeof(double);
     auto kern = rb.stats != nullptr ? screened_kernel<D, TP, true, true, false, true> : screened_kernel<D, TP, true, false, false, true>;
     if (int rc = allow_lds("screened", kern, lds)) return rc;
     RunBlock rbl = rb;
@@ -1416,7 +1494,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
             // (tools/bench_packing_shapes.py, 10^6 chains: vMF mixtures d = 10 K = 3 / 5 / 10 1.84 -> 2.35 / 1.62 -> 1.91 / 1.33 ->
             // 1.60e10 chain-steps/s, d = 8 K = 3 2.09 -> 2.58e10; equal occupancy: two per lane ahead by up to 10 %)
             int per_cu_one = 0;
-            if (!one_per_lane && resident_workgroups(reinterpret_cast<const void *>(kern), (TP::lds_doubles() + kTabLds) * sizeof(double), &per_cu_one) >= 1)
+            if (!one_per_lane && resident_workgroups(reinterpret_cast<const void *>(kern), (screen_row_doubles<TP>() + kTabLds) * sizeof(double), &per_cu_one) >= 1)
                 one_per_lane = per_cu_one > per_cu;
         }
     }
@@ -1438,7 +1516,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
         const char *env_st = getenv("GSSS_STATS_ONCHIP");
         if (rb.stats != nullptr && !(env_st && env_st[0] == '0') && rb.stats_lags <= kStatsMaxLags) {
             const size_t ring = (size_t)rb.stats_lags * kBlock;
-            if ((TP::lds_doubles() + kTabLds + ring) * sizeof(double) <= kMaxLdsBytes) {
+            if ((screen_row_doubles<TP>() + kTabLds + ring) * sizeof(double) <= kMaxLdsBytes) {
                 stats_onchip = 1;
                 stats_ring = ring;
                 one_per_lane = true;
@@ -1448,7 +1526,7 @@ int do_screened_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
     bool stage_rows = false;
     if (one_per_lane) {
         per_block = kBlock;
-        lds = (TP::lds_doubles() + kTabLds + stats_ring) * sizeof(double);  // nothing is parked: no LDS for it (statistics: the ring)
+        lds = (screen_row_doubles<TP>() + kTabLds + stats_ring) * sizeof(double);  // nothing is parked: no LDS for it (statistics: the ring)
         // A build of the kernel for ONE chain per lane (screened_kernel<.., STAGE>: no code for a parked chain -- Bingham d = 10: 154
         // instead of 143 registers, but nothing of the trade logic in the loop: 10^6 chains, 39.3 -> 36.85 ms, ahead of two chains
         // per lane at 37.45), which for the Bingham targets (TP::kHoldRows) also holds chain-major retained rows that are not whole
