@@ -349,10 +349,271 @@ def reference_chain(case, sampler):
     return out
 
 
+# ------------------------------------------------------------------------------------------ the baselines' reference chain
+MH_KINDS = ["rwmh", "indep", "mix", "hmc"]
+MH_FAMILIES = ["vmf3", "binghamfisher", "curve10", "gmix"]
+MH_CASES = [(f, d) for f in MH_FAMILIES for d in DIMS] + [(name, 0) for name in LAYOUT_CASES]
+# d = 5, 12 and 40 also run in every further cooperative layout that covers them (test_hip_mh_layouts.py)
+MH_FORCED = [(f, d) for d in (5, 12, 40) for f in ("vmf3", "binghamfisher")]
+MH_STEPS, MH_ADAPT, MH_LEAPFROG, MH_ALPHA = 8, 4, 3, 0.5
+# Two segments of a curve that both clip to the knot they share are a near-tie of near_tie_rows wherever the point lies in the
+# knot's cone -- a region, not a coincidence, and the start rows at the knots are in it, so no seed avoids it.  Their candidates
+# are the same knot up to the 1e-10 guard of the definition, y = sin(theta) b / (sin(theta) + 1e-10): the gradients differ by
+# kappa 1e-10 |1 / sin(theta_a) - 1 / sin(theta_b)| < 1e-8 for kappa = 300 and arcs of 0.25 .. 1 radian, which moves a state by
+# eps^2 1e-8 < 5e-11 per gradient.  mh_chain counts these apart (`same_knot`); a near-tie whose candidates' gradients differ by
+# more than TIE_GRAD is one at which the chain depends on the choice (`ties`), and no case may meet one.
+TIE_GRAD = 1e-8
+# the seed of a (family or name, d, kind) whose seed-0 chain misses a condition of test_reference_math.py::test_mh_chain_margins
+MH_SEEDS = {}
+
+
+# What the CPU oracle -- double arithmetic in the kernels' order of operations -- differs from the longdouble chain by, replaying
+# its draws: the largest (state, final momentum) deviation over every case of a (sampler class, layout family), rounded up to one
+# digit (test_reference_math.py::test_oracle_mh_against_reference_chain holds the oracle to it).  The stepsizes agree exactly.
+MH_YARDSTICK = {("rw", "lane"): (3e-15, 0.0), ("rw", "coop4"): (5e-16, 0.0), ("rw", "coop16"): (4e-16, 0.0), ("rw", "coop64"): (2e-16, 0.0),
+                ("hmc", "lane"): (1e-11, 7e-12), ("hmc", "coop4"): (6e-14, 8e-14), ("hmc", "coop16"): (2e-14, 7e-14),
+                ("hmc", "coop64"): (5e-15, 2e-13)}
+MH_CAPS = {"rw": (1e-10, 0.0), "hmc": (1e-9, 1e-7)}  # what the suite already allows (tests/test_hip_mh.py)
+MH_STEPSIZE_TOL = 1e-12
+
+
+def mh_bars(kind, d):
+    """-> (state bar, momentum bar) of the device against the longdouble chain: 16 times the yardstick -- a cooperative layout
+    sums d terms as a tree over up to 64 lanes x 32 slots where the oracle sums in sequence, each within d 2^-53 of the exact
+    value but not the same double -- rounded up to a power of ten, and never above what the suite already allows."""
+    cls = "hmc" if kind == "hmc" else "rw"
+    return tuple(min(cap, 10.0 ** np.ceil(np.log10(16.0 * y))) if y else 0.0
+                 for y, cap in zip(MH_YARDSTICK[cls, layout_family(d)], MH_CAPS[cls]))
+
+
+def layout_family(d):
+    """The four kinds of layout (GSSS_VEC_LIST): a lane per chain, then 4, 16 and 64 lanes per chain."""
+    return "lane" if d <= 10 else "coop4" if d <= 32 else "coop16" if d <= 128 else "coop64"
+
+
+# family or global-row case -> (concentration kappa, the random walk's largest eps, HMC's eps sqrt(kappa) up to d = 16, the power
+# of 16 / d it shrinks with above): what mh_stepsize starts from
+MH_SCALES = {"vmf3": (800.0, 0.07, 1.9, 0.25), "binghamfisher": (40.0, 1.5, 0.3, 0.0), "curve10": (300.0, 0.12, 0.8, 0.25),
+             "gmix": (50.0, 0.3, 1.6, 0.25), "vmf_k7000_d3": (10.0, 1.5, 1.0, 0.25), "vmf_k40_d600": (100.0, 0.2, 1.0, 0.25),
+             "curve_k60_d300": (300.0, 0.12, 0.8, 0.25), "gmix_d100_moved": (50.0, 0.3, 1.6, 0.25),
+             "gmix_d300_global": (50.0, 0.3, 1.6, 0.25), "gmix_d100_coop16x8": (30.0, 0.3, 1.6, 0.25)}
+# the cases whose acceptance share the rule leaves outside [0.1, 0.9] (test_reference_math.py::test_mh_chain_margins)
+MH_STEPSIZES = {("vmf3", 3, "rwmh"): 0.03, ("vmf3", 11, "rwmh"): 0.15, ("vmf3", 11, "hmc"): 0.15, ("curve10", 2, "hmc"): 0.08, ("gmix", 2, "hmc"): 0.3}
+
+
+def mh_family(family, d):
+    """The sweep family that stands for `family` at d: above d = 512 the dense Fisher-Bingham's place is taken by the diagonal
+    Bingham, whose longdouble reference needs d products where the dense one needs d^2 per evaluation."""
+    return "bingham_diag" if family == "binghamfisher" and d >= 513 else family
+
+
+def mh_steps(family, d):
+    """-> (steps, adapting steps): 8 and 4, so that the window ends inside the launch; the generic mixture above d = 1023 holds
+    two dense matrices, a longdouble pass over which takes a third of a second, and runs 4 and 2."""
+    return (4, 2) if family == "gmix" and d >= 1024 else (MH_STEPS, MH_ADAPT)
+
+
+def mh_stepsize(family, d, kind):
+    """The starting stepsize of a case, from the target's concentration kappa and d alone; test_mh_chain_margins holds every
+    case's acceptance share to [0.1, 0.9] with it.  The random-walk proposal normalise(r x + eps z), r ~ sqrt(d), moves by
+    eps z / sqrt(d): along the gradient log p changes by about kappa sin(angle to the mode) eps N(0, 1) / sqrt(d), several nats
+    either way at eps = 8 sqrt(d) / kappa; the step's length eps costs kappa eps^2 / 2 at a mode, which caps eps for the
+    concentrated families, while a Bingham of norm 20 is nearly flat in high dimension and takes steps of a radian.  HMC's
+    leapfrog is stable for eps sqrt(kappa) below 2, and its energy error grows with d, which eps ~ d^(-1/4) offsets above
+    d = 16."""
+    if (family, d, kind) in MH_STEPSIZES:
+        return MH_STEPSIZES[family, d, kind]
+    conc, cap, hmc, power = MH_SCALES[family]
+    if kind == "hmc":
+        return hmc / np.sqrt(conc) * min(1.0, (16.0 / d) ** power)
+    return min(8.0 * np.sqrt(d) / conc, cap)
+
+
+def _normalised(a):
+    return a / (np.sqrt(np.sum(a * a, axis=1)) + LD(1e-100))[:, None]
+
+
+def _dot(a, b):
+    return np.sum(a * b, axis=1)[:, None]
+
+
+def mh_chain(pdf, x0, kind, seed, n_steps, adapt_steps, stepsize, n_leapfrog=3, mixing_probability=0.5, draws=None):
+    """MetropolisHastings, IndependenceSampler, MixtureRWMHIndependenceSampler (`rwmh`, `indep`, `mix`) and SphericalHMC (`hmc`)
+    restated on reference_math.log_prob / gradient in longdouble, for every row of x0 at once:
+
+        rwmh    y = normalise(r x + eps z), r = sqrt(2 gamma(d / 2));  accept when log u < log p(y) - log p(x)
+        indep   y = normalise(z)
+        mix     a uniform below `mixing_probability` chooses rwmh, else indep; only rwmh proposals adapt eps, and only they count
+                towards the adaptation window
+        hmc     v = z - x (x.z);  H0 = v.v / 2 - log p(x);  w = v + eps / 2 P(x);  n_leapfrog times: with a = eps |w|,
+                (x, w) <- (x cos a + w / |w| sin a, w cos a - x |w| sin a), then w += eps P(x), the last time eps / 2 P(x);
+                x <- normalise(x);  H1 = w.w / 2 - log p(x);  accept when log u < H0 - H1 and then keep w as the momentum, else v.
+                P(x) = g - x (x.g), g the target's gradient at x
+        eps     x 1.02 after an accepted proposal, x 0.98 after a rejected one, for the first `adapt_steps` steps (mix: rwmh proposals)
+
+    normalise(a) = a / (|a| + 1e-100).  A state is carried to the next step as the double a device carries (so is the point at
+    which the target is evaluated: reference_math takes double rows), eps as a double product.  Per chain a step consumes -- the
+    order the `replay=` argument of the samplers expects -- (mix) the choice uniform, (an rwmh proposal) the gamma variate, d
+    normals, the accept uniform; they come from a seeded numpy Generator, or from `draws` (n, stride), and are recorded.
+
+    -> dict(states (n_steps, n, d), accept (n_steps, n) bool, n_accept (n,), stepsize (n,) final, stepsizes (n_steps, n) after
+    every step, trace: the same with NaN where the step made no rwmh proposal (every step of indep and hmc), n_rwmh, adapt_left
+    (n,), momenta (n, d) and momenta_steps (n_steps, n, d) (hmc, else zeros), replay (n, stride) padded with 0.5, margin: the
+    smallest |log u - log ratio|, share: accepted / proposed, ties / same_knot: gradients taken at a near-tie row of a curve target whose candidates differ / coincide, see TIE_GRAD)."""
+    assert kind in MH_KINDS
+    rng = np.random.default_rng(seed)
+    x = np.array(x0, dtype=np.float64)
+    n, d = x.shape
+    rows = np.full((n, n_steps * (d + 3) + 8), 0.5) if draws is None else np.array(draws, dtype=np.float64)
+    assert rows.shape[0] == n
+    cur = np.zeros(n, dtype=np.int64)
+    idx = np.arange(n)
+
+    def take(who, make):
+        if draws is None:
+            rows[who, cur[who]] = make(len(who))
+        vals = rows[who, cur[who]]
+        cur[who] += 1
+        return vals
+
+    def normals():
+        cols = cur[:, None] + np.arange(d)
+        if draws is None:
+            rows[idx[:, None], cols] = rng.standard_normal((n, d))
+        cur[:] += d
+        return rows[idx[:, None], cols].astype(LD)
+
+    curve = rm._kind(pdf) == "CurvedVonMisesFisher"
+    ties = same_knot = 0
+
+    def projected_gradient(at):
+        nonlocal ties, same_knot
+        P = at.astype(np.float64)
+        if curve:
+            tie, xy, gy = near_tie_rows(pdf, P, d)
+            for i in np.flatnonzero(tie):
+                tied = gy[i, xy[i].max() - xy[i] < 64 * d * 2.0 ** -53]
+                same_knot += 1
+                if float(np.max(np.abs(tied - tied[0]))) > TIE_GRAD:
+                    ties += 1
+        g = rm.gradient(pdf, P)
+        return g - at * _dot(at, g)
+
+    eps = np.broadcast_to(np.asarray(stepsize, dtype=np.float64), (n,)).copy()
+    left = np.full(n, int(adapt_steps), dtype=np.int64)
+    n_rwmh = np.zeros(n, dtype=np.int64)
+    n_accept = np.zeros(n, dtype=np.int64)
+    v = np.zeros((n, d))
+    states, momenta_steps = np.empty((n_steps, n, d)), np.zeros((n_steps, n, d))
+    accept = np.zeros((n_steps, n), dtype=bool)
+    stepsizes, trace = np.empty((n_steps, n)), np.full((n_steps, n), np.nan)
+    margin = np.inf
+    lp_x = rm.log_prob(pdf, x)
+    for s in range(n_steps):
+        xl = x.astype(LD)
+        use = np.zeros(n, dtype=bool)
+        if kind == "hmc":
+            z = normals()
+            p = z - xl * _dot(xl, z)
+            h0 = np.sum(p * p, axis=1) / 2 - lp_x
+            e = eps.astype(LD)[:, None]
+            y = xl
+            w = p + e / 2 * projected_gradient(y)
+            for leap in range(n_leapfrog):
+                nw = np.sqrt(_dot(w, w))
+                c, sn = np.cos(e * nw), np.sin(e * nw)
+                y, w = y * c + (w / nw) * sn, w * c - (y * nw) * sn
+                w = w + (e if leap < n_leapfrog - 1 else e / 2) * projected_gradient(y)
+            y = _normalised(y).astype(np.float64)
+            lp_y = rm.log_prob(pdf, y)
+            ratio = h0 - (np.sum(w * w, axis=1) / 2 - lp_y)
+        else:
+            if kind == "rwmh":
+                use[:] = True
+            elif kind == "mix":
+                use = take(idx, rng.random) < mixing_probability
+            r = np.zeros(n, dtype=LD)
+            who = idx[use]
+            if len(who):
+                r[who] = np.sqrt(2 * take(who, lambda m: rng.standard_gamma(0.5 * d, m)).astype(LD))
+            z = normals()
+            y = np.where(use[:, None], r[:, None] * xl + eps.astype(LD)[:, None] * z, z)
+            y = _normalised(y).astype(np.float64)
+            lp_y = rm.log_prob(pdf, y)
+            ratio = lp_y - lp_x
+        log_u = np.log(take(idx, rng.random).astype(LD))
+        ok = log_u < ratio
+        margin = min(margin, float(np.min(np.abs(log_u - ratio))))
+        x[ok] = y[ok]
+        lp_x = np.where(ok, lp_y, lp_x)
+        if kind == "hmc":
+            v = np.where(ok[:, None], w, p).astype(np.float64)
+            momenta_steps[s] = v
+        n_accept += ok
+        n_rwmh += use
+        if kind == "mix":
+            adapt = use & (left > 0)
+            left[adapt] -= 1
+        else:
+            adapt = np.full(n, s < adapt_steps)
+        eps[adapt] = eps[adapt] * np.where(ok[adapt], 1.02, 0.98)
+        states[s], accept[s], stepsizes[s] = x, ok, eps
+        trace[s, use] = eps[use]
+    stride = int(cur.max()) + 8
+    replay = np.full((n, stride), 0.5)
+    replay[:, :min(stride, rows.shape[1])] = rows[:, :stride]
+    return dict(states=states, accept=accept, n_accept=n_accept, stepsize=eps, stepsizes=stepsizes, trace=trace, n_rwmh=n_rwmh,
+                adapt_left=left, momenta=v, momenta_steps=momenta_steps, replay=replay, margin=margin,
+                share=float(accept.mean()), ties=ties, same_knot=same_knot)
+
+
+@functools.lru_cache(maxsize=None)
+def mh_case(family, d):
+    """-> (pdf, x0 (n_rows(d), d), layout name or None): a sweep case (family, d) or a global-row target (name, 0) with the
+    case's own rows as start points.  The curve and generic-mixture sweeps keep 7 rows above d = 512; seeded uniform rows bring
+    those to the 11 that fill two workgroups and part of a third."""
+    if d == 0:
+        return global_case(family)
+    pdf, X = sweep_case(mh_family(family, d), d)
+    if len(X) < n_rows(d):
+        X = np.concatenate([X, _unit(_rng("mh rows", family, d).standard_normal((n_rows(d) - len(X), d)))])
+    return pdf, X, None
+
+
+@functools.lru_cache(maxsize=None)
+def mh_reference(family, d, kind):
+    pdf, x0, _ = mh_case(family, d)
+    steps, adapt = mh_steps(family, d)
+    eps = mh_stepsize(family, pdf.d, kind)
+    out = mh_chain(pdf, x0, kind, MH_SEEDS.get((family, d, kind), 0), steps, adapt, eps, n_leapfrog=MH_LEAPFROG,
+                   mixing_probability=MH_ALPHA)
+    out.update(x0=x0, stepsize0=eps, steps=steps, adapt=adapt)
+    return out
+
+
+def oracle_target(orc, pdf):
+    """The CPU oracle's description of a target of ORACLE_FAMILIES (and of the vMF and curve targets of GLOBAL_CASES)."""
+    kind = rm._kind(pdf)
+    if kind == "VonMisesFisher":
+        return orc.Target.vmf_mixture(pdf.mu[None])
+    if kind == "MixtureModel":
+        # Target.vmf_mixture keeps the reference project's log(i0(kappa)), which overflows above kappa = 713; the sweep's
+        # mixtures reach kappa = 800, so the normalisers are formed here from the exponentially scaled Bessel function
+        from scipy.special import ive
+        mu = np.array([p.mu for p in pdf.pdfs])
+        kappa = np.linalg.norm(mu, axis=1)
+        return orc.Target(orc.VMF_MIXTURE, mu.shape[1], len(mu), mu=mu, lognorm=np.log(2 * np.pi) + np.log(ive(0, kappa)) + kappa,
+                          logw=np.log(pdf.weights))
+    if kind == "CurvedVonMisesFisher":
+        return orc.Target.curve_vmf(pdf.curve.knots, pdf.kappa)
+    return orc.Target.bingham(pdf.A, getattr(pdf, "b", None))
+
+
 def release():
     """Drop every cached case, and with it the device copies of the targets' parameters (gsss_target handles live on the
     distribution objects): a module that used the cases leaves the device as it found it."""
     import gc
-    for cache in (sweep_case, global_case, reference, chain_target, reference_chain):
+    for cache in (sweep_case, global_case, reference, chain_target, reference_chain, mh_case, mh_reference):
         cache.cache_clear()
+    rm._MATRICES.clear()
     gc.collect()

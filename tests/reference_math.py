@@ -26,6 +26,8 @@ calls none of the package's arithmetic, so it anchors both the CPU oracle and th
 Vector work (dots, quadratic forms) and the scalar transcendentals run in np.longdouble where it carries a 64-bit significand
 (x87 extended precision); `log_prob_mp` / `gradient_mp` evaluate the same definitions in mpmath at 50 digits -- the measure of
 the longdouble path's own error (tests/test_reference_math.py), and the path taken where longdouble is only a double."""
+import functools
+
 import mpmath
 import numpy as np
 
@@ -70,12 +72,19 @@ def _rows(X):
     return X.ndim == 1, np.atleast_2d(X).astype(LD)
 
 
-def _vmf_norm_ld(mu):
-    """|mu| in longdouble and log(2 pi) + log I0(|mu|): the Bessel function at the longdouble norm, from mpmath."""
+@functools.lru_cache(maxsize=16384)
+def _vmf_norm_of(mu_bytes):
     with mpmath.workdps(MP_DIGITS):
-        m = [mpmath.mpf(float(v)) for v in np.asarray(mu, dtype=np.float64)]
+        m = [mpmath.mpf(float(v)) for v in np.frombuffer(mu_bytes, dtype=np.float64)]
         kappa = mpmath.sqrt(mpmath.fsum(v * v for v in m))
         return _ld(mpmath.log(2 * mpmath.pi) + mpmath.log(mpmath.besseli(0, kappa)))
+
+
+def _vmf_norm_ld(mu):
+    """|mu| in longdouble and log(2 pi) + log I0(|mu|): the Bessel function at the longdouble norm, from mpmath.  A function of
+    the parameters alone, so the reference chains (layout_cases.mh_chain), which evaluate a target hundreds of times, form it
+    once per mu."""
+    return _vmf_norm_of(np.ascontiguousarray(mu, dtype=np.float64).tobytes())
 
 
 def curve_candidates(pdf, X):
@@ -100,6 +109,22 @@ def _curve_ld(pdf, x):
     return kappa * xy[r, best], kappa * y[r, best]
 
 
+_MATRICES = {}
+
+
+def _matrix_ld(A):
+    """A as longdouble; the conversion of the few large matrices last used is kept (a reference chain evaluates its target at
+    every step), keyed by the array itself."""
+    if A.size < 1 << 16:
+        return A.astype(LD)
+    hit = _MATRICES.get(id(A))
+    if hit is None or hit[0] is not A:
+        while len(_MATRICES) >= 4:
+            _MATRICES.pop(next(iter(_MATRICES)))
+        hit = _MATRICES[id(A)] = (A, A.astype(LD))
+    return hit[1]
+
+
 def _single_ld(pdf, x, want_grad):
     """(log_prob (n,), gradient (n, d) or None) of one non-mixture component at longdouble rows x."""
     kind = _kind(pdf)
@@ -110,8 +135,13 @@ def _single_ld(pdf, x, want_grad):
     if kind == "Uniform":
         return np.zeros(n, dtype=LD), (np.zeros_like(x) if want_grad else None)
     if kind in ("Bingham", "BinghamFisher"):
-        A = np.asarray(pdf.A, dtype=np.float64).astype(LD)
-        Ax = np.einsum("ij,nj->ni", A, x)                                        # x^T A x = x . (A x), whatever A
+        A64 = np.asarray(pdf.A, dtype=np.float64)
+        if d > 64 and np.count_nonzero(A64) == np.count_nonzero(A64.diagonal()):  # a diagonal A: the sum's zero terms left out
+            Ax = A64.diagonal().astype(LD) * x
+        else:
+            AL = _matrix_ld(A64)                                                 # x^T A x = x . (A x), whatever A
+            # (by blocks of rows that stay in cache while every point meets them: the same sums, sooner)
+            Ax = np.concatenate([np.einsum("ij,nj->ni", AL[i:i + 256], x) for i in range(0, d, 256)], axis=1)
         lp = np.sum(Ax * x, axis=-1)
         if kind == "BinghamFisher":
             lp = lp + x @ np.asarray(pdf.b, dtype=np.float64).astype(LD)
@@ -132,7 +162,13 @@ def _eval_ld(pdf, X, want_grad):
     else:
         terms = [(p, w) for p, w in flatten(pdf) if w > 0]                      # a zero weight adds no term
         vals, grads = [], []
-        for p, w in terms:
+        if len(terms) > 64 and all(_kind(p) == "VonMisesFisher" for p, _ in terms):
+            # thousands of vMF terms: the same terms, formed for all components at once (grads[k] below is then mu_k)
+            mus = np.array([p.mu for p, _ in terms], dtype=np.float64).astype(LD)
+            norms = np.array([_vmf_norm_ld(p.mu) for p, _ in terms], dtype=LD)
+            vals = list((x @ mus.T - norms + np.log(np.array([w for _, w in terms], dtype=LD))).T)
+            grads = None
+        for p, w in (terms if grads is not None else []):
             lp, g = _single_ld(p, x, want_grad)
             vals.append(lp + np.log(w))
             grads.append(g)
@@ -144,8 +180,8 @@ def _eval_ld(pdf, X, want_grad):
         g = None
         if want_grad:
             soft = e / s[:, None]
-            g = np.zeros_like(x)
-            for k, gk in enumerate(grads):
+            g = np.zeros_like(x) if grads is not None else soft @ mus
+            for k, gk in enumerate(grads or []):
                 g += soft[:, k:k + 1] * gk
     if single:
         return lp[0], (g[0] if want_grad else None)

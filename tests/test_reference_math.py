@@ -168,21 +168,7 @@ def test_registration_longdouble_against_mpmath(name):
 
 
 # ------------------------------------------------------------------------------------------ the oracle, at every d of the sweep
-def oracle_target(orc, pdf):
-    kind = rm._kind(pdf)
-    if kind == "VonMisesFisher":
-        return orc.Target.vmf_mixture(pdf.mu[None])
-    if kind == "MixtureModel":
-        # Target.vmf_mixture keeps the reference project's log(i0(kappa)), which overflows above kappa = 713; the sweep's
-        # mixtures reach kappa = 800, so the normalisers are formed here from the exponentially scaled Bessel function
-        from scipy.special import ive
-        mu = np.array([p.mu for p in pdf.pdfs])
-        kappa = np.linalg.norm(mu, axis=1)
-        return orc.Target(orc.VMF_MIXTURE, mu.shape[1], len(mu), mu=mu, lognorm=np.log(2 * np.pi) + np.log(ive(0, kappa)) + kappa,
-                          logw=np.log(pdf.weights))
-    if kind == "CurvedVonMisesFisher":
-        return orc.Target.curve_vmf(pdf.curve.knots, pdf.kappa)
-    return orc.Target.bingham(pdf.A, getattr(pdf, "b", None))
+oracle_target = lc.oracle_target  # (shared with test_hip_mh_layouts.py)
 
 
 # The bar is the oracle's own 1e-12, scaled by max(1, |value|): for log_prob the value itself, for a gradient the row's largest
@@ -276,6 +262,113 @@ def test_registration_chain_margins(case, sampler):
     ref = rc.reference_chain(case, sampler)
     print(f"{case} {sampler}: margin {ref['margin']:.2e}, tries {int(ref['tries'].sum())}, stride {ref['replay'].shape[1]}")
     assert ref["margin"] > lc.MIN_MARGIN
+
+
+# ------------------------------------------------------------------------------------------ the baselines' reference chain
+MH_FIXTURES = sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("mh_") and f.endswith(".npz")
+                     and str(golden(f)["target_kind"]) != "cpd")
+# HMC, longdouble against the reference's own double chain over the whole recorded horizon (the horizon test_oracle_mh.py uses
+# for these targets): states differ by up to 1.1e-10 (the README mixture at stepsize 0.1, beyond the integrator's stability
+# limit; 7.1e-11 on the dense Bingham, 2.3e-11 on the d = 10 curve, below 2e-11 elsewhere) and the momenta of every step by up
+# to 3.9e-9 (README mixture; 1.1e-9 on the d = 10 curve) -- two correct implementations, rounding amplified along 300 .. 600
+# transitions.  Sixteen times that, rounded up to a power of ten, is above what test_oracle_mh.py allows the oracle, so its bars
+# stand: 1e-9 for states, 1e-7 for the momenta of every step.
+HMC_FIXTURE_TOL, HMC_FIXTURE_MOMENTA_TOL = 1e-9, 1e-7
+
+
+@pytest.mark.parametrize("name", MH_FIXTURES)
+def test_mh_chain_reproduces_recorded_chain(name):
+    """layout_cases.mh_chain on the reference project's own recorded draws: every state, every accept flag, the counters, every
+    stepsize, HMC's momenta after every step."""
+    z = golden(name + ".npz")
+    kind, n = str(z["sampler"]), len(z["states"]) - 1
+    out = lc.mh_chain(product_target(z), z["x0"][None], kind, 0, n, int(z["burnin"]), float(z["stepsize0"]),
+                      n_leapfrog=int(z["n_leapfrog"]), mixing_probability=float(z["alpha"]) if kind == "mix" else 0.5,
+                      draws=z["draws"][None])
+    e_x = float(np.max(np.abs(out["states"][:, 0] - z["states"][1:])))
+    print(f"{name}: states {e_x:.1e}, margin {out['margin']:.1e}, near-ties {out['ties']} + {out['same_knot']} at a shared knot")
+    assert np.array_equal(out["accept"][:, 0], z["accept"].astype(bool))
+    assert int(out["n_accept"][0]) == int(z["n_accept"])
+    assert e_x < (HMC_FIXTURE_TOL if kind == "hmc" else KAT_TOL)
+    assert np.max(np.abs(out["stepsizes"][:, 0] / z["stepsize_trace"] - 1)) < 1e-13 and out["stepsize"][0] == out["stepsizes"][-1, 0]
+    assert out["ties"] == 0
+    if kind == "hmc":
+        e_v = float(np.max(np.abs(out["momenta_steps"][:, 0] - z["momenta_trace"][1:])))
+        print(f"{name}: momenta {e_v:.1e}")
+        assert e_v < HMC_FIXTURE_MOMENTA_TOL and np.max(np.abs(out["momenta"][0] - z["momenta"])) < HMC_FIXTURE_MOMENTA_TOL
+        assert np.all(np.isnan(out["trace"]))
+    else:
+        used = ~np.isnan(out["trace"][:, 0])
+        assert np.array_equal(used, z["use_rwmh"].astype(bool) if kind == "mix" else np.full(n, kind == "rwmh"))
+        assert int(out["n_rwmh"][0]) == int(used.sum())
+    if kind == "mix":
+        assert int(out["n_rwmh"][0]) == int(z["rwmh_counter"]) and n - int(out["n_rwmh"][0]) == int(z["indep_counter"])
+        assert np.max(np.abs(out["trace"][used, 0] / z["rwmh_stepsize_vals"] - 1)) < 1e-13
+        assert int(out["adapt_left"][0]) == max(0, int(z["burnin"]) - int(z["rwmh_counter"]))
+    # the recorded rows are the draws, in the order they were taken
+    assert np.array_equal(out["replay"][0, :len(z["draws"])], z["draws"])
+
+
+MH_ORACLE_CASES = [(f, d) for f, d in lc.MH_CASES if not f.startswith("gmix")]
+
+
+@pytest.mark.parametrize("family,d", MH_ORACLE_CASES)
+def test_oracle_mh_against_reference_chain(oracle, family, d):
+    """oracle.mh_run replaying the longdouble chain's draws: flags and counters equal, the stepsizes to 1e-12, and states and
+    momenta within the yardstick the device's bars are derived from (layout_cases.MH_YARDSTICK)."""
+    pdf, x0, _ = lc.mh_case(family, d)
+    tgt = lc.oracle_target(oracle, pdf)
+    for kind in lc.MH_KINDS:
+        ref = lc.mh_reference(family, d, kind)
+        sampler = {"rwmh": oracle.RWMH, "hmc": oracle.HMC, "indep": oracle.INDEP, "mix": oracle.MIX}[kind]
+        out = oracle.mh_run(tgt, x0, ref["steps"], sampler=sampler, stepsize=ref["stepsize0"], adapt_steps=ref["adapt"],
+                            n_leapfrog=lc.MH_LEAPFROG, replay=ref["replay"], trace=True, mixing_probability=lc.MH_ALPHA, n_threads=8)
+        assert np.all(out["err"] == 0)
+        assert np.array_equal(out["accept"].T.astype(bool), ref["accept"]) and np.array_equal(out["n_accept"], ref["n_accept"])
+        if kind == "mix":
+            assert np.array_equal(out["n_rwmh"], ref["n_rwmh"]) and np.array_equal(out["adapt_left"], ref["adapt_left"])
+            assert np.array_equal(out["use_rwmh"].T.astype(bool), ~np.isnan(ref["trace"]))
+        e_x = float(np.max(np.abs(out["samples"].transpose(1, 0, 2) - ref["states"])))
+        e_eps = float(np.max(np.abs(out["stepsize_trace"].T / ref["stepsizes"] - 1)))
+        e_v = rel(out["momenta"], ref["momenta"]) if kind == "hmc" else 0.0
+        y_x, y_v = lc.MH_YARDSTICK["hmc" if kind == "hmc" else "rw", lc.layout_family(pdf.d)]
+        print(f"{family} d={pdf.d} {kind} ({lc.layout_family(pdf.d)}): states {e_x:.1e} of {y_x:.0e}, stepsizes {e_eps:.1e}, "
+              f"momenta {e_v:.1e} of {y_v:.0e}")
+        assert e_eps < lc.MH_STEPSIZE_TOL and np.max(np.abs(out["stepsize"] / ref["stepsize"] - 1)) < lc.MH_STEPSIZE_TOL
+        assert e_x <= y_x and e_v <= y_v
+
+
+# vmf_k7000_d3 is 7000 vMF terms of kappa 10 .. 100 scattered over S^2: the terms overlap, log p varies by less than a nat between
+# the rows and their proposals, and no proposal kernel rejects a tenth of them at any stepsize (the independence sampler, whose
+# proposal ignores the stepsize, accepts 94 in 100).  Its random-walk and mixture chains are held to accepting AND rejecting.
+FLAT_CASES = {("vmf_k7000_d3", 0, "rwmh"), ("vmf_k7000_d3", 0, "mix")}
+
+
+@pytest.mark.parametrize("family,d", lc.MH_CASES + [c for c in lc.MH_FORCED if c not in lc.MH_CASES])
+def test_mh_chain_margins(family, d):
+    """The conditions test_hip_mh_layouts.py asserts of its cases, with nothing excluded: no proposal within 1e-8 of its
+    threshold, no gradient of HMC taken where a curve's candidates tie and differ, every chain set both accepting and
+    rejecting (a share of 0.1 .. 0.9; the independence sampler: see test_independence_sampler_accepts)."""
+    for kind in lc.MH_KINDS:
+        ref = lc.mh_reference(family, d, kind)
+        print(f"{family} d={d} {kind}: margin {ref['margin']:.1e}, accepted {ref['share']:.2f}, stepsize {ref['stepsize0']:.3g}, "
+              f"near-ties {ref['ties']} + {ref['same_knot']} at a shared knot")
+        assert ref["margin"] > lc.MIN_MARGIN
+        assert ref["ties"] == 0
+        assert len(ref["replay"]) == len(ref["x0"]) and (d == 0 or len(ref["x0"]) == lc.n_rows(d))
+        if (family, d, kind) in FLAT_CASES:
+            assert 0.0 < ref["share"] < 1.0
+        elif kind != "indep":
+            assert 0.1 <= ref["share"] <= 0.9
+        if kind == "mix":
+            assert 0 < ref["n_rwmh"].sum() < ref["accept"].size and np.any(ref["adapt_left"] == 0) and np.any(ref["adapt_left"] > 0)
+
+
+@pytest.mark.parametrize("family", lc.MH_FAMILIES + lc.LAYOUT_CASES)
+def test_independence_sampler_accepts(family):
+    """A uniform proposal against a kappa = 800 target is nearly always rejected: every family accepts one somewhere."""
+    cases = [(f, d) for f, d in lc.MH_CASES if f == family]
+    assert sum(int(lc.mh_reference(f, d, "indep")["n_accept"].sum()) for f, d in cases) > 0
 
 
 def test_curve_near_ties_are_rare():
