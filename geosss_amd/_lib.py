@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSSS_HIP_LIB") or os.path.join(_HERE, "libgsss_hip.so")  # env: side-by-side A/B builds
 
-VMF_MIXTURE, BINGHAM, CURVE_VMF, CPD, MIXTURE, USER = 1, 2, 3, 4, 5, 6
+VMF_MIXTURE, BINGHAM, CURVE_VMF, CPD, MIXTURE, USER, ACG = 1, 2, 3, 4, 5, 6, 7
 SHRINK, REJECT, RWMH, HMC, INDEP, MIX = 0, 1, 2, 3, 4, 5
 MODE_EXACT, MODE_FAST = 0, 1
 VARIANT_FAST_DOUBLE = 100

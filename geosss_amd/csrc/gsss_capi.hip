@@ -183,7 +183,8 @@ static int select_vec_for(const gsss::TargetBlock &tb, int variant)
     }
     switch (tb.kind) {
     case GSSS_VMF_MIXTURE: rows = (size_t)tb.k * dpad + (size_t)tb.k; break;
-    case GSSS_BINGHAM: rows = (size_t)(tb.d + 1) * dpad; break;
+    case GSSS_BINGHAM:
+    case GSSS_ACG: rows = (size_t)(tb.d + 1) * dpad; break;
     case GSSS_CURVE_VMF: rows = (size_t)tb.k * dpad + 4 * (size_t)(tb.k - 1); break;
     default: return vec;
     }
@@ -476,6 +477,9 @@ static int fast_refused(const gsss_target *t)
         set_error("fast mode is not built for a vMF mixture with d=%d, K=%d", tb.d, tb.k);
     else if (tb.kind == GSSS_BINGHAM)
         set_error("fast mode is not built for a Bingham target with d=%d", tb.d);
+    else if (tb.kind == GSSS_ACG)
+        set_error("fast mode is not built for an angular central Gaussian target with d=%d: the lane kernels cover d = 3 .. 10; "
+                  "use GSSS_MODE_EXACT", tb.d);
     else if (tb.kind == GSSS_CURVE_VMF)
         set_error("fast mode is not built for a curve-vMF target with d=%d, %d knots", tb.d, tb.k);
     else if (tb.kind == GSSS_MIXTURE) {
@@ -506,6 +510,7 @@ static int fast_launch(const FastPick &p, const TargetBlock &tb, const RunBlock 
     case GSSS_BINGHAM: return launch_fast_bingham(p, tb, rb, replay, st);
     case GSSS_CURVE_VMF: return launch_fast_curve(p, tb, rb, replay, st);
     case GSSS_MIXTURE: return launch_fast_mixture(p, tb, rb, replay, st);
+    case GSSS_ACG: return launch_fast_acg(p, tb, rb, replay, st);
     }
     return pick_error(p);
 }
@@ -514,7 +519,7 @@ static int fast_launch(const FastPick &p, const TargetBlock &tb, const RunBlock 
 // gsss_target_create_mixture
 struct PackedTarget {
     std::vector<double> blob;
-    bool bingham_diagonal = false;  // GSSS_BINGHAM: A is diagonal
+    bool bingham_diagonal = false;  // GSSS_BINGHAM, GSSS_ACG: A is diagonal
     double scale = 0.0;             // TargetBlock::scale
     int cpd_variant = 0;
 };
@@ -559,6 +564,48 @@ static int pack_target(const gsss_target_desc *desc, PackedTarget &out)
             out.bingham_diagonal = diag;
         }
         break;
+    case GSSS_ACG: {
+        if (!desc->A) {
+            set_error("angular central Gaussian needs A (the precision matrix Lambda)");
+            return GSSS_E_INVALID;
+        }
+        const double *L = desc->A;
+        bool diag = true;
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j < i; ++j) {
+                if (L[(size_t)i * d + j] != L[(size_t)j * d + i]) {
+                    set_error("angular central Gaussian: Lambda is not symmetric (Lambda[%d][%d] = %.17g, Lambda[%d][%d] = %.17g)", i, j,
+                              L[(size_t)i * d + j], j, i, L[(size_t)j * d + i]);
+                    return GSSS_E_INVALID;
+                }
+                if (L[(size_t)i * d + j] != 0.0) diag = false;
+            }
+        // positive definite: a Cholesky factorisation (lower triangle, row by row) finds a pivot that is not > 0, or a NaN / Inf.
+        // (d^3 / 6 products; eight running sums keep the additions from waiting on one another: under a second at d = 2048)
+        std::vector<double> c((size_t)d * d, 0.0);
+        for (int i = 0; i < d; ++i)
+            for (int j = 0; j <= i; ++j) {
+                const double *ci = &c[(size_t)i * d], *cj = &c[(size_t)j * d];
+                double part[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                int m = 0;
+                for (; m + 8 <= j; m += 8)
+                    for (int r = 0; r < 8; ++r) part[r] += ci[m + r] * cj[m + r];
+                for (; m < j; ++m) part[0] += ci[m] * cj[m];
+                const double s = L[(size_t)i * d + j] - (((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7])));
+                if (i == j) {
+                    if (!(s > 0.0) || !(s < INFINITY)) {
+                        set_error("angular central Gaussian: Lambda is not positive definite (Cholesky pivot %d is %g)", i, s);
+                        return GSSS_E_INVALID;
+                    }
+                    c[(size_t)i * d + i] = std::sqrt(s);
+                } else
+                    c[(size_t)i * d + j] = s / c[(size_t)j * d + j];
+            }
+        blob.assign(L, L + (size_t)d * d);
+        blob.insert(blob.end(), (size_t)d, 0.0);  // the row where Bingham keeps b: Acg<V> runs Bingham<V>'s quadratic form
+        out.bingham_diagonal = diag;
+        break;
+    }
     case GSSS_CURVE_VMF: {
         if (k < 2 || !desc->knots) {
             set_error("curve-vMF needs k >= 2 knots");
@@ -693,6 +740,7 @@ int gsss_target_create(const gsss_target_desc *desc, int device, gsss_target **o
     proto.tb.kind = desc->kind;
     proto.tb.d = d;
     proto.tb.k = desc->kind == GSSS_BINGHAM ? bingham_flags(pk.bingham_diagonal, desc) : k;
+    if (desc->kind == GSSS_ACG) proto.tb.k = pk.bingham_diagonal ? 1 : 0;  // bit 0 as for Bingham: a diagonal Lambda
     if (desc->kind == GSSS_CPD) proto.tb.k = k | (desc->n_target << 16);  // registration: both cloud sizes
     proto.tb.kappa = desc->kappa;
     proto.tb.scale = pk.scale;
@@ -965,6 +1013,7 @@ static int logprob_or_gradient(const gsss_target *t, const double *x_dev, int64_
     case GSSS_BINGHAM: return launch_logprob<Bingham>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_CURVE_VMF: return launch_logprob<CurveVmf>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_MIXTURE: return launch_logprob<Mixture>(vec, t->tb, x_dev, n, out_dev, grad, st);
+    case GSSS_ACG: return launch_logprob<Acg>(vec, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_CPD: return launch_cpd_logprob(t->cpd_variant, t->tb, x_dev, n, out_dev, grad, st);
     case GSSS_USER:
         if (grad && !t->user->has_gradient) {
@@ -1265,6 +1314,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
         case GSSS_BINGHAM: return launch_mh<Bingham>(vec, draws, a->sampler, t->tb, rb, mb, st);
         case GSSS_CURVE_VMF: return launch_mh<CurveVmf>(vec, draws, a->sampler, t->tb, rb, mb, st);
         case GSSS_MIXTURE: return launch_mh<Mixture>(vec, draws, a->sampler, t->tb, rb, mb, st);
+        case GSSS_ACG: return launch_mh<Acg>(vec, draws, a->sampler, t->tb, rb, mb, st);
         }
         set_error("corrupt target");
         return GSSS_E_INVALID;
@@ -1281,6 +1331,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
     case GSSS_BINGHAM: return launch_run<Bingham>(vec, draws, t->tb, rb, st);
     case GSSS_CURVE_VMF: return launch_run<CurveVmf>(vec, draws, t->tb, rb, st);
     case GSSS_MIXTURE: return launch_run<Mixture>(vec, draws, t->tb, rb, st);
+    case GSSS_ACG: return launch_run<Acg>(vec, draws, t->tb, rb, st);
     case GSSS_USER: return t->user->run(draws, t->tb, rb, st);
     }
     set_error("corrupt target");
@@ -1447,6 +1498,7 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
                       : t->tb.kind == GSSS_BINGHAM   ? "Bingham"
                       : t->tb.kind == GSSS_MIXTURE   ? "Mixture"
                       : t->tb.kind == GSSS_USER      ? "UserTarget"
+                      : t->tb.kind == GSSS_ACG       ? "Acg"
                                                      : "CurveVmf";
     if (vec[0]) snprintf(name, sizeof(name), "run_kernel<%s, %s%s>", vec, tgt, is_batch(t) ? ", batch" : "");
     return name;

@@ -1650,6 +1650,41 @@ struct Bingham {
     static constexpr int kScratchPerChain = (V::L == 1) ? 0 : V::DPAD + 1;
 };
 
+// Angular central Gaussian (distributions.py:199-206 with invC = Lambda): log p(y) = -(d / 2) log(y^T Lambda y).  The quadratic
+// form is Bingham's in every layout -- the blob is Lambda's rows followed by a zero row where Bingham keeps b, so the rows sit in
+// LDS or (d > 128) in global memory as there, behind the same fences around the scratch row.
+template <class V>
+struct Acg {
+    Bingham<V> quad;
+    double half_d;  // d / 2
+    __host__ __device__ static size_t lds_doubles(int k, int d) { return Bingham<V>::lds_doubles(k, d); }
+    __device__ void stage(double *lds, const TargetBlock &tb)
+    {
+        quad.stage(lds, tb);
+        half_d = 0.5 * (double)tb.d;
+    }
+    // q <= 0 or a non-finite q (a state off the sphere's finite points, a NaN row): NaN, which the samplers flag as non-finite
+    __device__ __forceinline__ static bool usable(double q) { return q > 0.0 && q < INFINITY; }
+    __device__ __forceinline__ double logp(const double (&y)[V::N], int g, double *scratch) const
+    {
+        const double q = quad.logp(y, g, scratch);  // (the zero row adds an exact +0.0)
+        return usable(q) ? -half_d * fm::log_fast(q) : NAN;
+    }
+    // -d Lambda y / q, with q = y . (Lambda y) from the same Lambda y: one pass over Lambda
+    __device__ __forceinline__ void grad(const double (&y)[V::N], int g, double *scratch, double (&out)[V::N]) const
+    {
+        quad.grad(y, g, scratch, out);  // 2 Lambda y
+        double q = 0.0;
+#pragma unroll
+        for (int i = 0; i < V::N; ++i) q = fma(0.5 * out[i], y[i], q);
+        q = V::reduce(q);
+        const double scale = usable(q) ? -half_d / q : NAN;  // (-d / q) (Lambda y) = (-d / 2 / q) (2 Lambda y)
+#pragma unroll
+        for (int i = 0; i < V::N; ++i) out[i] *= scale;
+    }
+    static constexpr int kScratchPerChain = Bingham<V>::kScratchPerChain;
+};
+
 template <class V>
 struct CurveVmf {
     const double *knots;   // LDS [K][DPAD]; nullptr: the rows are read from `knotsg` (rows_fit_lds)

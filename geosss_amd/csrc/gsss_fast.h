@@ -47,7 +47,7 @@ __device__ __forceinline__ double inv_norm(double s) { return s > 1e-200 ? rsqrt
 //                               first-step flag of round 1's carry scheme -- no target uses them any more.)
 //   level(cf, c, s)             level of y(theta); accept iff level > threshold
 //   kLinear                     level is a density (threshold = level(x) * U) rather than a
-//                               log-density (threshold = level(x) + log U)
+//                               log-density (threshold = level(x) + log U); FastAcg has a rule of its own (kPowerThreshold)
 // ------------------------------------------------------------------------------------------
 template <int D, int KC>
 struct FastVmf {
@@ -251,6 +251,84 @@ struct FastBingham {
     __device__ __forceinline__ double level(const Coef &cf, double c, double s) const
     {
         return fma(c * c, cf.qxx, fma(c * s, cf.qxu, (s * s) * cf.quu)) + fma(c, cf.bx, s * cf.bu);
+    }
+};
+
+// Angular central Gaussian: log p = -(D / 2) log q with q(theta) = c^2 xLx + c s (xLu + uLx) + s^2 uLu, Bingham's three
+// coefficients for A = Lambda.  The level is -q(theta), a try three FMAs and a comparison; the threshold rule is the policy's
+// own (kPowerThreshold below): p(y) > U p(x)  <=>  q(theta) < q(x) U^(-2/D), one log and one exp per step.
+template <int D>
+struct FastAcg {
+    const double *A;  // LDS [D][D]: Lambda
+    struct Coef {
+        double qxx, qxu, quu;
+        template <class F>
+        __device__ __forceinline__ void each(F &&f)
+        {
+            f(qxx);
+            f(qxu);
+            f(quu);
+        }
+    };
+    static constexpr int kCoefWords = 3;
+    __host__ __device__ static constexpr size_t lds_doubles() { return (size_t)D * D; }
+    bool diagonal;  // Lambda is diagonal: O(d) coefficients
+    __device__ void stage(double *lds, const TargetBlock &tb)
+    {
+        for (int i = threadIdx.x; i < D * D; i += kBlock) lds[i] = tb.blob[i];
+        A = lds;
+        diagonal = (tb.k & 1) != 0;
+    }
+    // returns q(x), formed from x as the exact kernels form it
+    __device__ __forceinline__ double make(Coef &cf, const double (&x)[D], const double (&u)[D], double /*lvl*/,
+                                           bool /*fresh*/) const
+    {
+        double qxx = 0.0, qxu = 0.0, quu = 0.0;
+        if (diagonal) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const double ajj = A[j * D + j];
+                const double xa = x[j] * ajj, ua = u[j] * ajj;
+                qxx = fma(xa, x[j], qxx);
+                qxu = fma(xa, u[j], fma(ua, x[j], qxu));
+                quu = fma(ua, u[j], quu);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double xa = 0.0, ua = 0.0;  // (x Lambda)_j, (u Lambda)_j: rows contracted first, as Acg<V>::logp does
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    const double aij = A[i * D + j];
+                    xa = fma(x[i], aij, xa);
+                    ua = fma(u[i], aij, ua);
+                }
+                qxx = fma(xa, x[j], qxx);
+                qxu = fma(xa, u[j], fma(ua, x[j], qxu));
+                quu = fma(ua, u[j], quu);
+                // one column at a time (as FastBingham does beyond d = 10): left alone the scheduler hoists the LDS reads of many
+                // columns, and the kernels take 6 .. 42 registers more -- a wavefront per SIMD fewer in most builds
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        cf.qxx = qxx;
+        cf.qxu = qxu;
+        cf.quu = quu;
+        return qxx;
+    }
+    __device__ __forceinline__ double level(const Coef &cf, double c, double s, double /*thr*/) const
+    {
+        return level(cf, c, s);
+    }
+    // the policy's own threshold rule (kPowerThreshold below): -q(x) U^(-2/D); U = 0 gives -inf, which every try passes
+    __device__ __forceinline__ static double threshold(double q0, double u_thr)
+    {
+        return -q0 * fm::exp_fast_k((-2.0 / D) * fm::log_fast(u_thr));
+    }
+    // -(y^T Lambda y) on the circle
+    __device__ __forceinline__ double level(const Coef &cf, double c, double s) const
+    {
+        return -fma(c * c, cf.qxx, fma(c * s, cf.qxu, (s * s) * cf.quu));
     }
 };
 
@@ -555,6 +633,19 @@ __device__ __forceinline__ void lds_trade(int32_t &a, int32_t &b, unsigned long 
     b = (int32_t)(uint32_t)(o >> 32);
 }
 
+// The threshold a step's tries are held against (accept iff level(theta) > threshold) is formed from the level of x that make()
+// returned, by one of three rules -- a compile-time trait of the target policy:
+//   kLinear             the level is a density:      threshold = level(x) U,        the chain goes on while 0 < level(x) < inf
+//   !kLinear            the level is a log-density:  threshold = level(x) + log U,  ... while -inf < level(x) < inf
+//   kPowerThreshold<TP> the policy's own rule, TP::threshold(level(x), U) (FastAcg: make() returns q(x) and the threshold is
+//                       -q(x) U^(-2/D)),                                            ... while 0 < level(x) < inf
+// The three sites that form `thr` (fast_kernel, coopfast_kernel, wave_kernel) keep the first two rules as they were written, so
+// that the kernels of every other policy stay what they were, and take the third in an `if constexpr` in front of them.
+template <class TP>
+inline constexpr bool kPowerThreshold = false;
+template <int D>
+inline constexpr bool kPowerThreshold<FastAcg<D>> = true;
+
 // a second chain per lane is parked in LDS only while that leaves room for >= 2 workgroups per CU
 template <int D, class TP>
 __host__ __device__ constexpr bool fast_parks()
@@ -753,7 +844,10 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
         }
         const double lvl0 = tp.make(cur.cf, cur.x, cur.u, cur.lvl, cur.steps_done == 0);
         bool finite;
-        if (TP::kLinear) {
+        if constexpr (kPowerThreshold<TP>) {
+            cur.thr = TP::threshold(lvl0, u_thr);
+            finite = lvl0 > 0.0 && lvl0 < INFINITY;
+        } else if (TP::kLinear) {
             cur.thr = lvl0 * u_thr;
             finite = lvl0 > 0.0 && lvl0 < INFINITY;
         } else {
@@ -988,6 +1082,7 @@ int do_fast(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool r
 // per-target launchers (one translation unit each, the lane kernels one per dimension): a switch over the pick's integers
 int launch_fast_vmf(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
 int launch_fast_bingham(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
+int launch_fast_acg(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
 int launch_fast_curve(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
 int launch_fast_mixture(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
 int launch_curvespec(const FastPick &p, const TargetBlock &tb, const RunBlock &rb, bool replay, hipStream_t st);
@@ -1386,7 +1481,10 @@ __global__ void __launch_bounds__(kBlock, V::N >= 16 ? 2 : 4) coopfast_kernel(Ta
             lvl0 = tp.level0(cf, lvl, s == 0);
         double thr;
         bool finite;
-        if (TP::kLinear) {
+        if constexpr (kPowerThreshold<TP>) {
+            thr = TP::threshold(lvl0, u_thr);
+            finite = lvl0 > 0.0 && lvl0 < INFINITY;
+        } else if (TP::kLinear) {
             thr = lvl0 * u_thr;
             finite = lvl0 > 0.0 && lvl0 < INFINITY;
         } else {
@@ -1655,7 +1753,10 @@ __global__ void __launch_bounds__(kBlock) wave_kernel(TargetBlock tb, RunBlock a
         const double lvl0 = tp.make(cf, x, u, lvl, s == 0);
         double thr;
         bool finite;
-        if (TP::kLinear) {
+        if constexpr (kPowerThreshold<TP>) {
+            thr = TP::threshold(lvl0, u_thr);
+            finite = lvl0 > 0.0 && lvl0 < INFINITY;
+        } else if (TP::kLinear) {
             thr = lvl0 * u_thr;
             finite = lvl0 > 0.0 && lvl0 < INFINITY;
         } else {

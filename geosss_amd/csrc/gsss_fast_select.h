@@ -16,10 +16,10 @@ constexpr double kScreenMaxKappa = 4000.0;  // margin ~ 2e-6 kappa: beyond this 
 constexpr int kMixFastTerms = 8;            // terms of the one FastMixture build per dimension
 
 enum FastFamily { kFamScreened, kFamFast, kFamWave, kFamCoopFast, kFamCurveSpec, kFamCurve64 };
-enum FastFlavour { kFlavVmf, kFlavBingham, kFlavBinghamDiag, kFlavCurve, kFlavMixture };
+enum FastFlavour { kFlavVmf, kFlavBingham, kFlavBinghamDiag, kFlavCurve, kFlavMixture, kFlavAcg };
 
 struct FastAsk {
-    int kind, d;     // GSSS_VMF_MIXTURE, GSSS_BINGHAM, GSSS_CURVE_VMF, GSSS_MIXTURE
+    int kind, d;     // GSSS_VMF_MIXTURE, GSSS_BINGHAM, GSSS_CURVE_VMF, GSSS_MIXTURE, GSSS_ACG
     int k;           // TargetBlock::k: components | Bingham flags (bit 0 a diagonal A, bit 1 a linear term) | knots; mix_info's terms
     bool mix_curve;  // GSSS_MIXTURE: mix_info's curve (a curve-vMF component)
     double scale;    // TargetBlock::scale
@@ -257,6 +257,17 @@ inline int select_mixture(const FastAsk &a, FastPick &p)
     return lane_pick(p, double_family(a), a.d, kMixFastTerms);
 }
 
+// GSSS_ACG: the all-double lane kernels at d = 3 .. 10 in every stream and placement that Bingham's all-double pick serves.  A try
+// is three double FMAs and a comparison already (FastAcg, gsss_fast.h), so there is no single-precision screen and a.screen does
+// not enter; no batch build, no cooperative kernel: other d are not built and mode "auto" runs the exact kernels
+inline int select_acg(const FastAsk &a, FastPick &p)
+{
+    p.flavour = kFlavAcg;
+    if (a.batch || a.d < 3 || a.d > 10) return GSSS_E_UNSUPPORTED;
+    p.lane = true;
+    return lane_pick(p, double_family(a), a.d);
+}
+
 }  // namespace fast_select_detail
 
 // GSSS_OK and the pick, or GSSS_E_UNSUPPORTED: fast mode has no kernel for this shape with these traits
@@ -269,6 +280,7 @@ inline int fast_select(const FastAsk &a, FastPick &p)
     case GSSS_BINGHAM: return fast_select_detail::select_bingham(a, p);
     case GSSS_CURVE_VMF: return fast_select_detail::select_curve(a, p);
     case GSSS_MIXTURE: return fast_select_detail::select_mixture(a, p);
+    case GSSS_ACG: return fast_select_detail::select_acg(a, p);
     }
     return GSSS_E_UNSUPPORTED;
 }
@@ -367,8 +379,8 @@ inline int batch_plan(int kind, int d, int k, long long n_targets, long long m, 
 // the instantiation a pick stands for, e.g. "screened_kernel<3, ScreenVmf<3, 3>>" (", batch" appended for the batch build)
 inline void fast_name(const FastPick &p, char *buf, size_t n)
 {
-    static const char *const kFlavour[] = {"Vmf", "Bingham", "BinghamDiag", "Curve", "Mixture"};
-    const char *flav = p.flavour >= 0 && p.flavour <= kFlavMixture ? kFlavour[p.flavour] : "?";
+    static const char *const kFlavour[] = {"Vmf", "Bingham", "BinghamDiag", "Curve", "Mixture", "Acg"};
+    const char *flav = p.flavour >= 0 && p.flavour <= kFlavAcg ? kFlavour[p.flavour] : "?";
     const bool bucketed = p.flavour == kFlavVmf || p.flavour == kFlavCurve || p.flavour == kFlavMixture;
     char kc[16] = "";
     if (bucketed) snprintf(kc, sizeof(kc), p.family == kFamCoopFast ? "<%d>" : ", %d", p.kc);

@@ -163,6 +163,32 @@ GSSS_HD double exp_fast(double x)
     return x == x ? ldexp(p, (int)n) : x;  // NaN stays NaN
 }
 
+// exp_fast with its constants read from scalar registers where they are used (GSSS_KC / GSSS_FMAK, as log_fast below):
+// the same operations in the same order, hence the same bits.  For a kernel's per-step set-up, where thirteen constants that
+// hipcc hoists out of the step loop cost 26 long-lived scalar registers (and, once those run out, vector lanes).
+GSSS_HD double exp_fast_k(double x)
+{
+    const double xc = fmin(fmax(x, -800.0), 800.0);
+    const double n = rint(xc * GSSS_KC(1.44269504088896338700e+00));
+    double r = fma(-n, GSSS_KC(6.93147180369123816490e-01), xc);
+    r = fma(-n, GSSS_KC(1.90821492927058770002e-10), r);
+    double p = GSSS_KC(1.6059043836821613e-10);
+    p = GSSS_FMAK(p, r, 2.08767569878680989792e-09);
+    p = GSSS_FMAK(p, r, 2.50521083854417187751e-08);
+    p = GSSS_FMAK(p, r, 2.75573192239858906526e-07);
+    p = GSSS_FMAK(p, r, 2.75573192239858906526e-06);
+    p = GSSS_FMAK(p, r, 2.48015873015873015873e-05);
+    p = GSSS_FMAK(p, r, 1.98412698412698412698e-04);
+    p = GSSS_FMAK(p, r, 1.38888888888888888889e-03);
+    p = GSSS_FMAK(p, r, 8.33333333333333333333e-03);
+    p = GSSS_FMAK(p, r, 4.16666666666666666667e-02);
+    p = GSSS_FMAK(p, r, 1.66666666666666666667e-01);
+    p = GSSS_FMAK(p, r, 0.5);
+    p = GSSS_FMAK(p, r, 1.0);
+    p = GSSS_FMAK(p, r, 1.0);
+    return x == x ? ldexp(p, (int)n) : x;  // NaN stays NaN
+}
+
 // log(x) for finite normal x > 0 (fdlibm's s = f/(2+f) series, |err| < 1 ulp); x = 0 -> -inf
 GSSS_HD double log_fast(double x)
 {

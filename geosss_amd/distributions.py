@@ -128,7 +128,7 @@ class Distribution:
         """-> (kind, d, k, kappa, (mu, logc, A, knots))"""
         raise TypeError(f"{type(self).__name__} has no device parameter block: the samplers run inside HIP kernels and cannot call a "
                         "Python log_prob; built-in targets are VonMisesFisher, Bingham, BinghamFisher, CurvedVonMisesFisher, "
-                        "Uniform, MixtureModel (of any of these), CoherentPointDrift and GaussianMixtureModel")
+                        "Uniform, MixtureModel (of any of these), AngularCentralGaussian, CoherentPointDrift and GaussianMixtureModel")
 
     def _device_target(self, device=None):
         dev = _device_index(device)
@@ -262,8 +262,8 @@ class _HostDensity(Distribution):
 
     def _pack(self):
         raise TypeError(f"{type(self).__name__} is a host-side density (plotting / envelope); the HIP samplers run on "
-                        "VonMisesFisher, Bingham, BinghamFisher, CurvedVonMisesFisher, Uniform, MixtureModel (of any of these) "
-                        "and the registration targets")
+                        "VonMisesFisher, Bingham, BinghamFisher, CurvedVonMisesFisher, Uniform, MixtureModel (of any of these), "
+                        "AngularCentralGaussian and the registration targets")
 
 
 class MarginalVonMisesFisher(_HostDensity, VonMisesFisher):
@@ -317,6 +317,64 @@ class ACG(MultivariateNormal):
     @counted
     def log_prob(self, x):
         return -0.5 * self.d * np.log(self._quad(x))
+
+
+class AngularCentralGaussian(Distribution):
+    """Angular central Gaussian as a sampler target: log_prob = -(d / 2) log(x^T Lambda x), unnormalised, with the precision
+    matrix Lambda = C^-1 symmetric positive definite (distributions.py:199-206 with invC = Lambda).  Runs on kernels of its own
+    (GSSS_ACG): both slice samplers in exact and, at d = 3 .. 10, fast mode, and the four Metropolis-Hastings / HMC classes;
+    log_prob and gradient = -d Lambda x / (x^T Lambda x) are evaluated on the device.  `ACG` stays the host-side overlay;
+    `.host()` gives the equivalent one.  Not a MixtureModel component or TargetBatch member."""
+
+    def __init__(self, precision):
+        L = np.array(precision, dtype=np.float64)
+        if L.ndim != 2 or L.shape[0] != L.shape[1] or L.shape[0] < 2 or not np.all(np.isfinite(L)):
+            raise ValueError("precision must be a finite square matrix (d >= 2)")
+        if not np.max(np.abs(L - L.T)) <= 1e-10 * np.max(np.abs(L)):  # (rounding of an inverse or of Q diag Q^T passes)
+            raise ValueError("precision must be symmetric")
+        L = 0.5 * (L + L.T)  # symmetric to the last bit, which the library asks for
+        try:
+            np.linalg.cholesky(L)
+        except np.linalg.LinAlgError:
+            raise ValueError("precision must be positive definite") from None
+        self.precision = L
+
+    @classmethod
+    def from_covariance(cls, C):
+        """The target with Lambda = C^-1."""
+        C = np.array(C, dtype=np.float64)
+        if C.ndim != 2 or C.shape[0] != C.shape[1]:
+            raise ValueError("C must be a square matrix")
+        return cls(np.linalg.inv(C))
+
+    @property
+    def d(self):
+        return len(self.precision)
+
+    @property
+    def mode(self):
+        """An axis of largest density (the density is antipodally symmetric): the eigenvector of Lambda's smallest eigenvalue."""
+        return np.linalg.eigh(self.precision)[1][:, 0]
+
+    @property
+    def max_log_prob(self):
+        return -0.5 * self.d * float(np.log(np.linalg.eigvalsh(self.precision)[0]))
+
+    def host(self):
+        """The equivalent host-side `ACG` (covariance Lambda^-1)."""
+        return ACG(np.linalg.inv(self.precision))
+
+    def _pack(self):
+        return _lib.ACG, self.d, 0, 0.0, (None, None, _as_f64(self.precision), None)
+
+    @counted
+    def log_prob(self, x):
+        return self._log_prob_device(x)
+
+    @counted
+    def gradient(self, x):
+        """-d Lambda x / (x^T Lambda x), on the device."""
+        return self._gradient_device(x)
 
 
 class MixtureModel(Distribution):

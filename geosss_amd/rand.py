@@ -6,11 +6,12 @@ path); unlike the reference, which reads numpy's global stream, they take a `see
     sample_vMF(pdf, size=1, seed=None)                 geosss/rand.py:31-66
     sample_bingham(A, n_samples, n_iter=1000, ...)     geosss/rand.py:145-193 (sample_bingham_2d / _3d: the same target
                                                        through the general scheme)
+    sample_acg(pdf, size, seed=None)                   exact i.i.d. draws of an AngularCentralGaussian, on the host
 """
 import numpy as np
 import torch
 
-from .distributions import Bingham, VonMisesFisher
+from .distributions import ACG, AngularCentralGaussian, Bingham, VonMisesFisher
 from .sphere import _device_index
 
 
@@ -148,3 +149,20 @@ def sample_bingham_3d(pdf, n_samples=1, **kw):
     if not (isinstance(pdf, Bingham) and pdf.d == 3):
         raise ValueError("3D Bingham expected")
     return sample_bingham(pdf, n_samples, **kw)
+
+
+def sample_acg(pdf, size, seed=None):
+    """`size` exact independent draws from an angular central Gaussian: x = L^-T z / |L^-T z| with Lambda = L L^T and z
+    standard normal, so that L^-T z ~ N(0, Lambda^-1).  Host arithmetic on numpy's generator (one-shot ground truth for a
+    test or an experiment).  `pdf`: an AngularCentralGaussian, or a host-side ACG.  Returns (size, d)."""
+    if isinstance(pdf, AngularCentralGaussian):
+        precision = pdf.precision
+    elif isinstance(pdf, ACG):
+        precision = 0.5 * (pdf.invC + pdf.invC.T)
+    else:
+        raise TypeError("sample_acg expects an AngularCentralGaussian (or a host-side ACG)")
+    rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(seed)
+    L = np.linalg.cholesky(precision)
+    z = rng.standard_normal((int(size), len(precision)))
+    y = np.linalg.solve(L.T, z.T).T
+    return y / np.linalg.norm(y, axis=1, keepdims=True)

@@ -46,6 +46,12 @@ extern "C" {
 #define GSSS_USER 6        /* a density the user writes in C++ (Distribution subclassed, distributions.py:16-25), compiled into a module of
                               its own for ONE vector layout and made by gsss_target_create_user, never by gsss_target_create.
                               GSSS_MODE_EXACT only; no mixture component. */
+#define GSSS_ACG 7         /* ACG :199-206: log p(x) = -(d / 2) log(x^T Lambda x), unnormalised.  gsss_target_desc::A
+                              carries Lambda [d][d], symmetric positive definite (GSSS_E_INVALID otherwise: gsss_target_create checks
+                              the symmetry and runs a host Cholesky); mu, logc, knots and k are unused.  Every exact layout, the four
+                              MH / HMC samplers, log_prob and gradient = -d Lambda x / (x^T Lambda x).  Fast mode: d = 3 .. 10, the
+                              all-double lane kernels (the accept test q(theta) < q(x) U^(-2/d) needs no logarithm per try, so there
+                              is no single-precision screen); other d: GSSS_E_UNSUPPORTED.  No mixture component, no batch member. */
 
 /* samplers (geosss/mcmc.py) */
 #define GSSS_SHRINK 0 /* ShrinkageSphericalSliceSampler.__next__  :382-401 */
@@ -94,6 +100,7 @@ typedef struct gsss_target gsss_target; /* opaque; owns a small device parameter
  *   BINGHAM:     A[d][d] symmetric (distributions.py:67-70); if mu is non-NULL it is the vector b[d] of a
  *       BinghamFisher target, log_prob = x^T A x + x.b (distributions.py:106-114).
  *   CURVE_VMF:   knots[k][d] unit vectors, kappa (distributions.py:263-265).
+ *   ACG:         A[d][d] = Lambda = C^-1, symmetric positive definite (distributions.py:199-206 with invC = Lambda).
  *   CPD:         see the fields below; GSSS_MODE_EXACT, lane-per-chain kernels; samplers GSSS_SHRINK / GSSS_REJECT / GSSS_RWMH.
  */
 typedef struct gsss_target_desc {
