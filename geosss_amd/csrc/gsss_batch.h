@@ -38,14 +38,6 @@ inline int batch_grid_fits(int64_t grid)
 template <class V, template <class> class TT>
 int do_run_batch(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
 {
-    using T = TT<V>;
-    const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>() + PhiloxDraws<V>::kLdsDoubles) * sizeof(double);
-    if (lds > kMaxLdsBytes) {
-        set_error("target parameters need %zu B of LDS (> %zu)", lds, kMaxLdsBytes);
-        return GSSS_E_UNSUPPORTED;
-    }
-    auto kern = run_kernel<V, TT, PhiloxDraws, false, true, BatchBlock>;
-    if (int rc = allow_lds("run batch", kern, lds)) return rc;
     const int64_t per_block = (V::L == 1 && rb.spread) ? kBlock / 64 : kBlock / V::L;
     BatchBlock bb;
     bb.stride = bi.stride;
@@ -53,10 +45,11 @@ int do_run_batch(const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi,
     bb.chunks = (int32_t)ceil_div(bi.m, per_block);
     const int64_t grid = (rb.n_chains / bi.m) * (int64_t)bb.chunks;
     if (int rc = batch_grid_fits(grid)) return rc;
-    return launch_kernel("run batch", kern, grid, lds, st, nullptr, tb, rb, bb);
+    return launch_exact<V, TT, PhiloxDraws<V>::kLdsDoubles>("run batch", run_kernel<V, TT, PhiloxDraws, false, true, BatchBlock>, grid, st,
+                                                            tb, rb, bb);
 }
-int launch_batch_run_vmf(int vec_id, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st);
-int launch_batch_run_bingham(int vec_id, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st);
+// the batch's family (vMF mixtures, else Bingham) in the layout vec_id: gsss_batch_exact.hip
+int launch_batch_run(int vec_id, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st);
 
 // fast mode: one chain per lane, nothing parked, never sliced -- whatever the placement asked for
 inline RunBlock batch_lane_args(const RunBlock &rb)

@@ -4,28 +4,13 @@
 
 namespace gsss {
 
-int launch_batch_run_vmf(int vec_id, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
+int launch_batch_run(int vec_id, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
 {
-    switch (vec_id) {
-#define GSSS_CASE(ID, V, NAME) \
-    case ID: return do_run_batch<V, VmfMixture>(tb, rb, bi, st);
-        GSSS_VEC_LIST(GSSS_CASE)
-#undef GSSS_CASE
-    }
-    set_error("unknown vector layout %d", vec_id);
-    return GSSS_E_INVALID;
-}
-
-int launch_batch_run_bingham(int vec_id, const TargetBlock &tb, const RunBlock &rb, const BatchInfo &bi, hipStream_t st)
-{
-    switch (vec_id) {
-#define GSSS_CASE(ID, V, NAME) \
-    case ID: return do_run_batch<V, Bingham>(tb, rb, bi, st);
-        GSSS_VEC_LIST(GSSS_CASE)
-#undef GSSS_CASE
-    }
-    set_error("unknown vector layout %d", vec_id);
-    return GSSS_E_INVALID;
+    const bool vmf = tb.kind == GSSS_VMF_MIXTURE;
+    return with_layout(vec_id, [&](auto v) {
+        using V = decltype(v);
+        return vmf ? do_run_batch<V, VmfMixture>(tb, rb, bi, st) : do_run_batch<V, Bingham>(tb, rb, bi, st);
+    });
 }
 
 }  // namespace gsss

@@ -9,20 +9,13 @@ namespace {
 template <class V, template <class> class TT>
 int do_batch_logprob(const TargetBlock &tb, BatchPoints a, int64_t n_targets, bool grad, hipStream_t st)
 {
-    using T = TT<V>;
-    const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>()) * sizeof(double);
-    if (lds > kMaxLdsBytes) {
-        set_error("target parameters need %zu B of LDS (> %zu)", lds, kMaxLdsBytes);
-        return GSSS_E_UNSUPPORTED;
-    }
     const int64_t chunks = ceil_div(a.n, kBlock / V::L);
     // (n_targets is an int32's: the product cannot overflow once chunks fits one)
     const int64_t grid = chunks > 0x7FFFFFFFll ? chunks : n_targets * chunks;
     if (int rc = batch_grid_fits(grid)) return rc;
     a.chunks = (int32_t)chunks;
     auto kern = grad ? batch_logprob_kernel<V, TT, true> : batch_logprob_kernel<V, TT, false>;
-    if (int rc = allow_lds("batch logprob", kern, lds)) return rc;
-    return launch_kernel("batch logprob", kern, grid, lds, st, nullptr, tb, a);
+    return launch_exact<V, TT, 0>("batch logprob", kern, grid, st, tb, a);
 }
 
 }  // namespace
@@ -34,14 +27,10 @@ int launch_batch_logprob(int vec_id, const TargetBlock &tb, BatchPoints a, int64
         return GSSS_E_UNSUPPORTED;
     }
     const bool vmf = tb.kind == GSSS_VMF_MIXTURE;
-    switch (vec_id) {
-#define GSSS_CASE(ID, V, NAME) \
-    case ID: return vmf ? do_batch_logprob<V, VmfMixture>(tb, a, n_targets, grad, st) : do_batch_logprob<V, Bingham>(tb, a, n_targets, grad, st);
-        GSSS_VEC_LIST(GSSS_CASE)
-#undef GSSS_CASE
-    }
-    set_error("unknown vector layout %d", vec_id);
-    return GSSS_E_INVALID;
+    return with_layout(vec_id, [&](auto v) {
+        using V = decltype(v);
+        return vmf ? do_batch_logprob<V, VmfMixture>(tb, a, n_targets, grad, st) : do_batch_logprob<V, Bingham>(tb, a, n_targets, grad, st);
+    });
 }
 
 }  // namespace gsss

@@ -155,6 +155,31 @@ int select_vec(int d, int variant)
     return GSSS_E_UNSUPPORTED;
 }
 
+// The built-in families of exact mode, one row a target kind: the policy's name as gsss_kernel_name prints it, its launchers
+// (gsss_target_<family>.hip, gsss_mh_<family>.hip) and the rows select_vec_for budgets (NULL: Mixture sizes its whole launch).
+// Registration and user targets are not here: they dispatch on cpd_variant and on the module's table.
+struct ExactFamily {
+    int kind;
+    const char *name;
+    decltype(&launch_run<VmfMixture>) run;
+    decltype(&launch_logprob<VmfMixture>) logprob;
+    decltype(&launch_mh<VmfMixture>) mh;
+    size_t (*row_doubles)(int k, int d, size_t dpad);
+};
+#define GSSS_FAMILY(KIND, TT, ROWS) {KIND, #TT, launch_run<TT>, launch_logprob<TT>, launch_mh<TT>, ROWS}
+static const ExactFamily kExactFamilies[] = {
+    GSSS_FAMILY(GSSS_VMF_MIXTURE, VmfMixture, vmf_row_doubles), GSSS_FAMILY(GSSS_BINGHAM, Bingham, bingham_row_doubles),
+    GSSS_FAMILY(GSSS_CURVE_VMF, CurveVmf, curve_row_doubles),   GSSS_FAMILY(GSSS_MIXTURE, Mixture, nullptr),
+    GSSS_FAMILY(GSSS_ACG, Acg, bingham_row_doubles),
+};
+#undef GSSS_FAMILY
+static const ExactFamily *exact_family(int kind)
+{
+    for (const ExactFamily &f : kExactFamilies)
+        if (f.kind == kind) return &f;
+    return nullptr;
+}
+
 // The layout an exact-mode launch of this target runs in: select_vec's -- unless the target's rows (component means, knots, a
 // dense A) do not fit a workgroup's LDS in it: then the smallest sixty-four-lane layout, whose kernels read such rows from global
 // memory (rows_fit_lds, gsss_device.h).  A layout forced by the caller stays as asked.
@@ -164,31 +189,23 @@ static int select_vec_for(const gsss::TargetBlock &tb, int variant)
     if (vec < 0 || variant != 0) return vec;
     int n;
     const VecInfo *v = vec_table(&n);
-    size_t dpad = 0;
+    size_t dpad = 0, L = 1;
     for (int i = 0; i < n; ++i)
-        if (v[i].id == vec) dpad = (size_t)v[i].dpad;
+        if (v[i].id == vec) {
+            dpad = (size_t)v[i].dpad;
+            L = (size_t)v[i].L;
+        }
     if (dpad >= 256) return vec;
-    size_t rows = 0;
+    bool fits = true;
     if (tb.kind == GSSS_MIXTURE) {  // the whole launch: component slots, Bingham scratch rows, draw tables and rows (Mixture)
-        int L = 1;
-        for (int i = 0; i < n; ++i)
-            if (v[i].id == vec) L = v[i].L;
         const MixInfo mi = mix_info(tb);
-        const size_t need = (size_t)mi.n * 8 + (L > 1 ? (dpad + 1) * (size_t)(kBlock / L) : 0) + kMixDrawsReserve +
+        const size_t need = (size_t)mi.n * kMixSlotReserve + (L > 1 ? (dpad + 1) * ((size_t)kBlock / L) : 0) + kMixDrawsReserve +
                             (size_t)mi.rows * dpad + (size_t)mi.extra;
-        if (need * sizeof(double) <= kMaxLdsBytes) return vec;
-        for (int i = 0; i < n; ++i)
-            if (!v[i].exact_dim && v[i].dpad >= 256 && tb.d <= v[i].dpad) return v[i].id;
-        return vec;
+        fits = need * sizeof(double) <= kMaxLdsBytes;
+    } else if (const ExactFamily *f = exact_family(tb.kind)) {
+        fits = f->row_doubles(tb.k, tb.d, dpad) * sizeof(double) <= gsss::kRowsLdsBytes;
     }
-    switch (tb.kind) {
-    case GSSS_VMF_MIXTURE: rows = (size_t)tb.k * dpad + (size_t)tb.k; break;
-    case GSSS_BINGHAM:
-    case GSSS_ACG: rows = (size_t)(tb.d + 1) * dpad; break;
-    case GSSS_CURVE_VMF: rows = (size_t)tb.k * dpad + 4 * (size_t)(tb.k - 1); break;
-    default: return vec;
-    }
-    if (rows * sizeof(double) <= gsss::kRowsLdsBytes) return vec;
+    if (fits) return vec;
     for (int i = 0; i < n; ++i)
         if (!v[i].exact_dim && v[i].dpad >= 256 && tb.d <= v[i].dpad) return v[i].id;
     return vec;
@@ -1008,14 +1025,9 @@ static int logprob_or_gradient(const gsss_target *t, const double *x_dev, int64_
     DeviceGuard guard(t->device);
     if (!guard.ok) return GSSS_E_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (t->tb.kind) {
-    case GSSS_VMF_MIXTURE: return launch_logprob<VmfMixture>(vec, t->tb, x_dev, n, out_dev, grad, st);
-    case GSSS_BINGHAM: return launch_logprob<Bingham>(vec, t->tb, x_dev, n, out_dev, grad, st);
-    case GSSS_CURVE_VMF: return launch_logprob<CurveVmf>(vec, t->tb, x_dev, n, out_dev, grad, st);
-    case GSSS_MIXTURE: return launch_logprob<Mixture>(vec, t->tb, x_dev, n, out_dev, grad, st);
-    case GSSS_ACG: return launch_logprob<Acg>(vec, t->tb, x_dev, n, out_dev, grad, st);
-    case GSSS_CPD: return launch_cpd_logprob(t->cpd_variant, t->tb, x_dev, n, out_dev, grad, st);
-    case GSSS_USER:
+    if (const ExactFamily *f = exact_family(t->tb.kind)) return f->logprob(vec, t->tb, x_dev, n, out_dev, grad, st);
+    if (t->tb.kind == GSSS_CPD) return launch_cpd_logprob(t->cpd_variant, t->tb, x_dev, n, out_dev, grad, st);
+    if (t->tb.kind == GSSS_USER) {
         if (grad && !t->user->has_gradient) {
             set_error("this user target defines no gsss_user_gradient");
             return GSSS_E_UNSUPPORTED;
@@ -1263,8 +1275,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
             if (fast_select(fast_ask(t, rb.screen, false), pick) != GSSS_OK) return fast_refused(t);
             return fast_launch(pick, tbb, rb, t->batch, false, st);
         }
-        return tbb.kind == GSSS_VMF_MIXTURE ? launch_batch_run_vmf(vec, tbb, rb, t->batch, st)
-                                            : launch_batch_run_bingham(vec, tbb, rb, t->batch, st);
+        return launch_batch_run(vec, tbb, rb, t->batch, st);
     }
     const int draws = replay ? kDrawsReplay : (a->rng_state_dev ? kDrawsNumpy : kDrawsPhilox);
     if (a->mode == GSSS_MODE_FAST) {
@@ -1309,13 +1320,7 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
             }
             return t->user->mh(draws, a->sampler, t->tb, rb, mb, st);
         }
-        switch (t->tb.kind) {
-        case GSSS_VMF_MIXTURE: return launch_mh<VmfMixture>(vec, draws, a->sampler, t->tb, rb, mb, st);
-        case GSSS_BINGHAM: return launch_mh<Bingham>(vec, draws, a->sampler, t->tb, rb, mb, st);
-        case GSSS_CURVE_VMF: return launch_mh<CurveVmf>(vec, draws, a->sampler, t->tb, rb, mb, st);
-        case GSSS_MIXTURE: return launch_mh<Mixture>(vec, draws, a->sampler, t->tb, rb, mb, st);
-        case GSSS_ACG: return launch_mh<Acg>(vec, draws, a->sampler, t->tb, rb, mb, st);
-        }
+        if (const ExactFamily *f = exact_family(t->tb.kind)) return f->mh(vec, draws, a->sampler, t->tb, rb, mb, st);
         set_error("corrupt target");
         return GSSS_E_INVALID;
     }
@@ -1326,14 +1331,8 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
         }
         return launch_cpd_run(t->cpd_variant, draws, t->tb, rb, st);
     }
-    switch (t->tb.kind) {
-    case GSSS_VMF_MIXTURE: return launch_run<VmfMixture>(vec, draws, t->tb, rb, st);
-    case GSSS_BINGHAM: return launch_run<Bingham>(vec, draws, t->tb, rb, st);
-    case GSSS_CURVE_VMF: return launch_run<CurveVmf>(vec, draws, t->tb, rb, st);
-    case GSSS_MIXTURE: return launch_run<Mixture>(vec, draws, t->tb, rb, st);
-    case GSSS_ACG: return launch_run<Acg>(vec, draws, t->tb, rb, st);
-    case GSSS_USER: return t->user->run(draws, t->tb, rb, st);
-    }
+    if (const ExactFamily *f = exact_family(t->tb.kind)) return f->run(vec, draws, t->tb, rb, st);
+    if (t->tb.kind == GSSS_USER) return t->user->run(draws, t->tb, rb, st);
     set_error("corrupt target");
     return GSSS_E_INVALID;
 }
@@ -1494,12 +1493,8 @@ const char *gsss_kernel_name(const gsss_target *t, int32_t mode, int32_t variant
         return name;
     }
     const char *vec = gsss_variant_name(t, mode, variant);
-    const char *tgt = t->tb.kind == GSSS_VMF_MIXTURE ? "VmfMixture"
-                      : t->tb.kind == GSSS_BINGHAM   ? "Bingham"
-                      : t->tb.kind == GSSS_MIXTURE   ? "Mixture"
-                      : t->tb.kind == GSSS_USER      ? "UserTarget"
-                      : t->tb.kind == GSSS_ACG       ? "Acg"
-                                                     : "CurveVmf";
+    const ExactFamily *f = exact_family(t->tb.kind);
+    const char *tgt = f ? f->name : t->tb.kind == GSSS_USER ? "UserTarget" : "CurveVmf";  // (a registration handle prints CurveVmf)
     if (vec[0]) snprintf(name, sizeof(name), "run_kernel<%s, %s%s>", vec, tgt, is_batch(t) ? ", batch" : "");
     return name;
 }

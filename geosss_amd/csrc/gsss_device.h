@@ -1426,6 +1426,11 @@ __host__ __device__ constexpr bool rows_fit_lds(size_t doubles)
 {
     return V::DPAD < 256 || doubles * sizeof(double) <= kRowsLdsBytes;
 }
+// The rows of a target in a layout of `dpad` columns, per family: what the policies below stage (in_lds, lds_doubles) and what
+// select_vec_for (gsss_capi.hip) holds against kRowsLdsBytes before a layout is chosen.
+__host__ __device__ constexpr size_t vmf_row_doubles(int k, int /*d*/, size_t dpad) { return (size_t)k * dpad + (size_t)k; }
+__host__ __device__ constexpr size_t bingham_row_doubles(int /*k*/, int d, size_t dpad) { return (size_t)(d + 1) * dpad; }
+__host__ __device__ constexpr size_t curve_row_doubles(int k, int /*d*/, size_t dpad) { return (size_t)k * dpad + 4 * (size_t)(k - 1); }
 // component c of a row: LDS rows are padded with zeros, global rows end at d
 template <bool GLOBAL, class V>
 __device__ __forceinline__ double row_at(const double *row, int c, int d)
@@ -1444,8 +1449,8 @@ struct VmfMixture {
     int K, d;
     static constexpr bool kMayGlobal = V::DPAD >= 256;  // (rows_fit_lds)
 
-    __host__ __device__ static bool in_lds(int k) { return rows_fit_lds<V>((size_t)k * V::DPAD + k); }
-    __host__ __device__ static size_t lds_doubles(int k, int /*d*/) { return in_lds(k) ? (size_t)k * V::DPAD + k : 0; }
+    __host__ __device__ static bool in_lds(int k) { return rows_fit_lds<V>(vmf_row_doubles(k, 0, V::DPAD)); }
+    __host__ __device__ static size_t lds_doubles(int k, int /*d*/) { return in_lds(k) ? vmf_row_doubles(k, 0, V::DPAD) : 0; }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         K = tb.k;
@@ -1527,8 +1532,8 @@ struct Bingham {
     int d;
     static constexpr bool kMayGlobal = V::DPAD >= 256;  // (rows_fit_lds)
     // (host and device take the same decision from (d, DPAD): 136 KB leave room for the groups' scratch rows and the tables)
-    __host__ __device__ static bool in_lds(int d) { return rows_fit_lds<V>((size_t)(d + 1) * V::DPAD); }
-    __host__ __device__ static size_t lds_doubles(int /*k*/, int d) { return in_lds(d) ? (size_t)(d + 1) * V::DPAD : (size_t)V::DPAD; }
+    __host__ __device__ static bool in_lds(int d) { return rows_fit_lds<V>(bingham_row_doubles(0, d, V::DPAD)); }
+    __host__ __device__ static size_t lds_doubles(int /*k*/, int d) { return in_lds(d) ? bingham_row_doubles(0, d, V::DPAD) : (size_t)V::DPAD; }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         d = tb.d;
@@ -1693,8 +1698,8 @@ struct CurveVmf {
     int K, d;
     double kappa;
     static constexpr bool kMayGlobal = V::DPAD >= 256;  // (rows_fit_lds)
-    __host__ __device__ static bool in_lds(int k) { return rows_fit_lds<V>((size_t)k * V::DPAD + 4 * (size_t)(k - 1)); }
-    __host__ __device__ static size_t lds_doubles(int k, int /*d*/) { return in_lds(k) ? (size_t)k * V::DPAD + 4 * (size_t)(k - 1) : 0; }
+    __host__ __device__ static bool in_lds(int k) { return rows_fit_lds<V>(curve_row_doubles(k, 0, V::DPAD)); }
+    __host__ __device__ static size_t lds_doubles(int k, int /*d*/) { return in_lds(k) ? curve_row_doubles(k, 0, V::DPAD) : 0; }
     __device__ void stage(double *lds, const TargetBlock &tb)
     {
         K = tb.k;
@@ -1799,6 +1804,7 @@ constexpr int kMixMaxComponents = 16;
 constexpr int kMixMaxRows = 1 << 20;  // parameter rows of all components (TargetBlock::dpad), and their further doubles
 constexpr int kMixHeader = 8;
 constexpr int kMixDrawsReserve = 768;  // NumpyDraws<V>::kLdsDoubles, the largest draw-source table
+constexpr int kMixSlotReserve = 8;     // doubles select_vec_for (gsss_capi.hip) budgets per component policy (Mixture::kSlotDoubles)
 
 struct MixInfo {
     int n, nb, terms;
@@ -1837,6 +1843,7 @@ struct Mixture {
     static constexpr bool kMayGlobal = V::DPAD >= 256;  // (rows_fit_lds)
     static constexpr int kScratchPerChain = Bingham<V>::kScratchPerChain;
     static constexpr size_t kSlotDoubles = (sizeof(Slot) + sizeof(double) - 1) / sizeof(double);
+    static_assert(kSlotDoubles <= kMixSlotReserve, "select_vec_for budgets kMixSlotReserve doubles per component policy");
 
     __host__ __device__ static size_t lds_doubles(int k, int /*d*/) { return (size_t)(k & 31) * kSlotDoubles; }
     __host__ __device__ static size_t rows_offset(const TargetBlock &tb)

@@ -49,6 +49,31 @@ int select_vec(int d, int variant);
 
 // draw source of a launch
 enum : int { kDrawsPhilox = 0, kDrawsReplay = 1, kDrawsNumpy = 2 };
+template <template <class> class DR>
+struct DrawSource {};
+
+// f(DrawSource<DR>{}) for the DR a launch's draw source names: the launchers below deduce DR from the tag
+template <class F>
+int with_draws(int draws, F &&f)
+{
+    if (draws == kDrawsReplay) return f(DrawSource<ReplayDraws>{});
+    if (draws == kDrawsNumpy) return f(DrawSource<NumpyDraws>{});
+    return f(DrawSource<PhiloxDraws>{});
+}
+
+// f(V{}) for the vector layout with this id
+template <class F>
+int with_layout(int vec_id, F &&f)
+{
+    switch (vec_id) {
+#define GSSS_LAYOUT_CASE(ID, V, NAME) \
+    case ID: return f(V{});
+        GSSS_VEC_LIST(GSSS_LAYOUT_CASE)
+#undef GSSS_LAYOUT_CASE
+    }
+    set_error("unknown vector layout %d", vec_id);
+    return GSSS_E_INVALID;
+}
 
 template <template <class> class TT>
 int launch_run(int vec_id, int draws, const TargetBlock &tb, const RunBlock &rb, hipStream_t st);
@@ -64,56 +89,72 @@ int launch_logprob(int vec_id, const TargetBlock &tb, const double *x, int64_t n
         }                                                                               \
     } while (0)
 
-template <class V, template <class> class TT, template <class> class DR>
-int do_run(const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
+// The dynamic LDS of an exact-mode launch of TT<V>, in doubles: the policy's rows, the lane groups' scratch rows, then kDraws
+// doubles for the draw source's tables (0: the logprob kernels) -- the regions run_kernel, logprob_kernel and mh_kernel address.
+// A policy that lays its LDS out itself (Mixture: launch_doubles) keeps a fixed reserve for the tables in the middle of it.
+template <class T, class = void>
+constexpr bool kOwnLdsLayout = false;
+template <class T>
+constexpr bool kOwnLdsLayout<T, decltype((void)T::launch_doubles(TargetBlock{}))> = true;
+
+template <class V, template <class> class TT, int kDraws>
+size_t exact_lds_doubles(const TargetBlock &tb)
 {
     using T = TT<V>;
-    const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>() + DR<V>::kLdsDoubles) * sizeof(double);
+    if constexpr (kOwnLdsLayout<T>) {
+        static_assert(kDraws <= kMixDrawsReserve, "the draw source's tables must fit the reserve");
+        return T::launch_doubles(tb);
+    } else {
+        return T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>() + (size_t)kDraws;
+    }
+}
+
+// The one launch of an exact-mode kernel: its LDS by the rule above, refused beyond a workgroup's; kern(tb, args...) on `grid`
+// workgroups.
+template <class V, template <class> class TT, int kDraws, class Kern, class... Args>
+int launch_exact(const char *family, Kern kern, int64_t grid, hipStream_t st, const TargetBlock &tb, const Args &...args)
+{
+    const size_t lds = exact_lds_doubles<V, TT, kDraws>(tb) * sizeof(double);
     if (lds > kMaxLdsBytes) {
         set_error("target parameters need %zu B of LDS (> %zu)", lds, kMaxLdsBytes);
         return GSSS_E_UNSUPPORTED;
     }
+    if (int rc = allow_lds(family, kern, lds)) return rc;
+    return launch_kernel(family, kern, grid, lds, st, nullptr, tb, args...);
+}
+
+template <class V, template <class> class TT, template <class> class DR>
+int do_run(DrawSource<DR>, const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
+{
     auto kern = run_kernel<V, TT, DR, false>;
     if (rb.stats != nullptr) kern = run_kernel<V, TT, DR, true>;  // running statistics: a second build, so that the plain kernels carry none of it
-    if (int rc = allow_lds("run", kern, lds)) return rc;
     const int64_t per_block = (V::L == 1 && rb.spread) ? kBlock / 64 : kBlock / V::L;
-    return launch_kernel("run", kern, ceil_div(rb.n_chains, per_block), lds, st, nullptr, tb, rb);
+    return launch_exact<V, TT, DR<V>::kLdsDoubles>("run", kern, ceil_div(rb.n_chains, per_block), st, tb, rb);
 }
 
-template <class V, template <class> class TT>
+// (GRAD = false: a target without a gradient builds the value kernel alone)
+template <class V, template <class> class TT, bool GRAD = true>
 int do_logprob(const TargetBlock &tb, const double *x, int64_t n, double *out, bool grad, hipStream_t st)
 {
-    using T = TT<V>;
-    const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>()) * sizeof(double);
-    if (lds > kMaxLdsBytes) {
-        set_error("target parameters need %zu B of LDS (> %zu)", lds, kMaxLdsBytes);
-        return GSSS_E_UNSUPPORTED;
-    }
-    auto kern = grad ? logprob_kernel<V, TT, true> : logprob_kernel<V, TT, false>;
-    if (int rc = allow_lds("logprob", kern, lds)) return rc;
-    return launch_kernel("logprob", kern, ceil_div(n, kBlock / V::L), lds, st, nullptr, tb, x, n, out);
+    auto kern = logprob_kernel<V, TT, false>;
+    if constexpr (GRAD)
+        if (grad) kern = logprob_kernel<V, TT, true>;
+    return launch_exact<V, TT, 0>("logprob", kern, ceil_div(n, kBlock / V::L), st, tb, x, n, out);
 }
 
-// Each target's translation unit expands this once.
-#define GSSS_DEFINE_TARGET_LAUNCHERS(TT)                                                                      \
-    template <>                                                                                               \
-    int launch_run<TT>(int vec_id, int draws, const TargetBlock &tb, const RunBlock &rb, hipStream_t st)       \
-    {                                                                                                         \
-        switch (vec_id) {                                                                                     \
-            GSSS_VEC_LIST(GSSS_RUN_CASE_##TT)                                                                  \
-        }                                                                                                     \
-        set_error("unknown vector layout %d", vec_id);                                                        \
-        return GSSS_E_INVALID;                                                                                \
-    }                                                                                                         \
-    template <>                                                                                               \
-    int launch_logprob<TT>(int vec_id, const TargetBlock &tb, const double *x, int64_t n, double *out,         \
-                           bool grad, hipStream_t st)                                                         \
-    {                                                                                                         \
-        switch (vec_id) {                                                                                     \
-            GSSS_VEC_LIST(GSSS_LOGPROB_CASE_##TT)                                                              \
-        }                                                                                                     \
-        set_error("unknown vector layout %d", vec_id);                                                        \
-        return GSSS_E_INVALID;                                                                                \
+// Each target's translation unit expands this once: run_kernel and logprob_kernel in every vector layout.
+#define GSSS_DEFINE_TARGET_LAUNCHERS(TT)                                                                                       \
+    template <>                                                                                                                \
+    int launch_run<TT>(int vec_id, int draws, const TargetBlock &tb, const RunBlock &rb, hipStream_t st)                        \
+    {                                                                                                                          \
+        return with_layout(vec_id, [&](auto v) {                                                                               \
+            return with_draws(draws, [&](auto dr) { return do_run<decltype(v), TT>(dr, tb, rb, st); });                        \
+        });                                                                                                                    \
+    }                                                                                                                          \
+    template <>                                                                                                                \
+    int launch_logprob<TT>(int vec_id, const TargetBlock &tb, const double *x, int64_t n, double *out, bool grad, hipStream_t st) \
+    {                                                                                                                          \
+        return with_layout(vec_id, [&](auto v) { return do_logprob<decltype(v), TT>(tb, x, n, out, grad, st); });              \
     }
 
 }  // namespace gsss

@@ -186,47 +186,34 @@ __global__ void __launch_bounds__(kBlock) mh_kernel(TargetBlock tb, RunBlock a, 
     dr.finish(a, c, active && g == 0);
 }
 
-template <class V, template <class> class TT, template <class> class DR, int SAMPLER>
-int do_mh(const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStream_t st)
+template <class V, template <class> class TT, int SAMPLER, template <class> class DR>
+int do_mh(DrawSource<DR>, const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStream_t st)
 {
-    using T = TT<V>;
-    const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<V, T>() + DR<V>::kLdsDoubles) * sizeof(double);
-    if (lds > kMaxLdsBytes) {
-        set_error("target parameters need %zu B of LDS", lds);
-        return GSSS_E_UNSUPPORTED;
-    }
-    auto kern = mh_kernel<V, TT, DR, SAMPLER>;
-    if (int rc = allow_lds("MH", kern, lds)) return rc;
-    return launch_kernel("MH", kern, ceil_div(rb.n_chains, kBlock / V::L), lds, st, nullptr, tb, rb, mb);
+    return launch_exact<V, TT, DR<V>::kLdsDoubles>("MH", mh_kernel<V, TT, DR, SAMPLER>, ceil_div(rb.n_chains, kBlock / V::L), st, tb, rb, mb);
 }
 
 template <template <class> class TT>
 int launch_mh(int vec_id, int draws, int sampler, const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStream_t st);
 
-// one layout: every draw source x both samplers
-template <class V, template <class> class TT>
+// one layout: every draw source x both kernels (HMC = false: a target without a gradient builds the RWMH kernels alone)
+template <class V, template <class> class TT, bool HMC = true>
 int mh_dispatch(int draws, int sampler, const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStream_t st)
 {
-    if (sampler == GSSS_RWMH || sampler == GSSS_INDEP || sampler == GSSS_MIX) {  // one kernel, the proposal chosen at run time (mb.kind)
-        if (draws == kDrawsReplay) return do_mh<V, TT, ReplayDraws, GSSS_RWMH>(tb, rb, mb, st);
-        if (draws == kDrawsNumpy) return do_mh<V, TT, NumpyDraws, GSSS_RWMH>(tb, rb, mb, st);
-        return do_mh<V, TT, PhiloxDraws, GSSS_RWMH>(tb, rb, mb, st);
-    }
-    if (draws == kDrawsReplay) return do_mh<V, TT, ReplayDraws, GSSS_HMC>(tb, rb, mb, st);
-    if (draws == kDrawsNumpy) return do_mh<V, TT, NumpyDraws, GSSS_HMC>(tb, rb, mb, st);
-    return do_mh<V, TT, PhiloxDraws, GSSS_HMC>(tb, rb, mb, st);
+    const bool rwmh = sampler == GSSS_RWMH || sampler == GSSS_INDEP || sampler == GSSS_MIX;  // one kernel, the proposal chosen at run time (mb.kind)
+    return with_draws(draws, [&](auto dr) {
+        if constexpr (HMC)
+            if (!rwmh) return do_mh<V, TT, GSSS_HMC>(dr, tb, rb, mb, st);
+        return do_mh<V, TT, GSSS_RWMH>(dr, tb, rb, mb, st);
+    });
 }
 
+// Each target's translation unit expands this once: mh_kernel in every vector layout.
 #define GSSS_DEFINE_MH_LAUNCHER(TT)                                                                              \
     template <>                                                                                                  \
     int launch_mh<TT>(int vec_id, int draws, int sampler, const TargetBlock &tb, const RunBlock &rb,             \
                       const MhBlock &mb, hipStream_t st)                                                         \
     {                                                                                                            \
-        switch (vec_id) {                                                                                        \
-            GSSS_VEC_LIST(GSSS_MH_CASE_##TT)                                                                     \
-        }                                                                                                        \
-        set_error("unknown vector layout %d", vec_id);                                                           \
-        return GSSS_E_INVALID;                                                                                   \
+        return with_layout(vec_id, [&](auto v) { return mh_dispatch<decltype(v), TT>(draws, sampler, tb, rb, mb, st); }); \
     }
 
 }  // namespace gsss

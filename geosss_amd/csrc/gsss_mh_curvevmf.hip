@@ -3,8 +3,5 @@
 #include "gsss_mh.h"
 
 namespace gsss {
-#define GSSS_MH_CASE_CurveVmf(ID, V, NAME) \
-    case ID:                        \
-        return mh_dispatch<V, CurveVmf>(draws, sampler, tb, rb, mb, st);
 GSSS_DEFINE_MH_LAUNCHER(CurveVmf)
 }  // namespace gsss

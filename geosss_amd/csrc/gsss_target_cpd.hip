@@ -223,9 +223,7 @@ template <class V> using Cpd24W = CpdTargetT<V, 24, false>;
 template <template <class> class TT>
 static int cpd_run(int draws, const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 {
-    if (draws == kDrawsReplay) return do_run<VL4, TT, ReplayDraws>(tb, rb, st);
-    if (draws == kDrawsNumpy) return do_run<VL4, TT, NumpyDraws>(tb, rb, st);
-    return do_run<VL4, TT, PhiloxDraws>(tb, rb, st);
+    return with_draws(draws, [&](auto dr) { return do_run<VL4, TT>(dr, tb, rb, st); });
 }
 template <template <class> class TT>
 static int cpd_rwmh(int draws, int sampler, const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStream_t st)

@@ -33,43 +33,25 @@ using UV = UserVec<GSSS_USER_VEC>::type;
 static int user_run(int draws, const TargetBlock &tb, const RunBlock &rb, hipStream_t st)
 {
     static_assert(NumpyDraws<UV>::kLdsDoubles <= kMixDrawsReserve, "the draw source's tables must fit UserTarget's reserve");
-    if (draws == kDrawsReplay) return do_run<UV, UserTarget, ReplayDraws>(tb, rb, st);
-    if (draws == kDrawsNumpy) return do_run<UV, UserTarget, NumpyDraws>(tb, rb, st);
-    return do_run<UV, UserTarget, PhiloxDraws>(tb, rb, st);
+    return with_draws(draws, [&](auto dr) { return do_run<UV, UserTarget>(dr, tb, rb, st); });
 }
 
 static int user_logprob(const TargetBlock &tb, const double *x, int64_t n, double *out, bool grad, hipStream_t st)
 {
-    using T = UserTarget<UV>;
-    const size_t lds = (T::lds_doubles(tb.k, tb.d) + scratch_doubles<UV, T>()) * sizeof(double);
-    auto kern = logprob_kernel<UV, UserTarget, false>;
-    if (grad) {
-        if constexpr (kUserHasGradient) {
-            kern = logprob_kernel<UV, UserTarget, true>;
-        } else {
-            set_error("this user target defines no gsss_user_gradient");
-            return GSSS_E_UNSUPPORTED;
-        }
+    if (grad && !kUserHasGradient) {
+        set_error("this user target defines no gsss_user_gradient");
+        return GSSS_E_UNSUPPORTED;
     }
-    if (int rc = allow_lds("logprob", kern, lds)) return rc;
-    return launch_kernel("logprob", kern, ceil_div(n, kBlock / UV::L), lds, st, nullptr, tb, x, n, out);
+    return do_logprob<UV, UserTarget, kUserHasGradient>(tb, x, n, out, grad, st);
 }
 
 static int user_mh(int draws, int sampler, const TargetBlock &tb, const RunBlock &rb, const MhBlock &mb, hipStream_t st)
 {
-    if (sampler == GSSS_RWMH || sampler == GSSS_INDEP || sampler == GSSS_MIX) {
-        if (draws == kDrawsReplay) return do_mh<UV, UserTarget, ReplayDraws, GSSS_RWMH>(tb, rb, mb, st);
-        if (draws == kDrawsNumpy) return do_mh<UV, UserTarget, NumpyDraws, GSSS_RWMH>(tb, rb, mb, st);
-        return do_mh<UV, UserTarget, PhiloxDraws, GSSS_RWMH>(tb, rb, mb, st);
-    }
-    if constexpr (kUserHasGradient) {
-        if (draws == kDrawsReplay) return do_mh<UV, UserTarget, ReplayDraws, GSSS_HMC>(tb, rb, mb, st);
-        if (draws == kDrawsNumpy) return do_mh<UV, UserTarget, NumpyDraws, GSSS_HMC>(tb, rb, mb, st);
-        return do_mh<UV, UserTarget, PhiloxDraws, GSSS_HMC>(tb, rb, mb, st);
-    } else {
+    if (!kUserHasGradient && sampler != GSSS_RWMH && sampler != GSSS_INDEP && sampler != GSSS_MIX) {
         set_error("spherical HMC needs the target's gradient: this user target defines no gsss_user_gradient");
         return GSSS_E_UNSUPPORTED;
     }
+    return mh_dispatch<UV, UserTarget, kUserHasGradient>(draws, sampler, tb, rb, mb, st);
 }
 
 static const UserModuleTable kTable = {kUserModuleAbi, GSSS_ABI_VERSION, GSSS_USER_VEC, kUserHasGradient ? 1 : 0,
