@@ -639,12 +639,36 @@ __device__ __forceinline__ void lds_trade(int32_t &a, int32_t &b, unsigned long 
 //   !kLinear            the level is a log-density:  threshold = level(x) + log U,  ... while -inf < level(x) < inf
 //   kPowerThreshold<TP> the policy's own rule, TP::threshold(level(x), U) (FastAcg: make() returns q(x) and the threshold is
 //                       -q(x) U^(-2/D)),                                            ... while 0 < level(x) < inf
-// The three sites that form `thr` (fast_kernel, coopfast_kernel, wave_kernel) keep the first two rules as they were written, so
-// that the kernels of every other policy stay what they were, and take the third in an `if constexpr` in front of them.
 template <class TP>
 inline constexpr bool kPowerThreshold = false;
 template <int D>
 inline constexpr bool kPowerThreshold<FastAcg<D>> = true;
+
+// The rule above, for the three kernels that form a threshold (fast_kernel, coopfast_kernel, wave_kernel).  finite: the chain goes on.
+struct SliceThreshold {
+    double thr;
+    bool finite;
+};
+template <class TP>
+__device__ __forceinline__ SliceThreshold slice_threshold(double lvl0, double u_thr)
+{
+    if constexpr (kPowerThreshold<TP>) {
+        return {TP::threshold(lvl0, u_thr), lvl0 > 0.0 && lvl0 < INFINITY};
+    } else if (TP::kLinear) {
+        return {lvl0 * u_thr, lvl0 > 0.0 && lvl0 < INFINITY};
+    } else {
+        return {lvl0 + fm::log_fast(u_thr), lvl0 > -INFINITY && lvl0 < INFINITY};
+    }
+}
+
+// a step's tries go into the launch's count, saturating (fast_kernel, screened_kernel)
+template <class Chain>
+__device__ __forceinline__ void count_tries(Chain &cur)
+{
+    const uint32_t sum = cur.n_try + (uint32_t)cur.t;
+    if (sum < cur.n_try) cur.err |= GSSS_CHAIN_COUNTER_SATURATED;  // > 2^32-1 proposals in one launch
+    cur.n_try = sum < cur.n_try ? 0xFFFFFFFFu : sum;
+}
 
 // a second chain per lane is parked in LDS only while that leaves room for >= 2 workgroups per CU
 template <int D, class TP>
@@ -694,6 +718,35 @@ __device__ __forceinline__ int32_t stage_shared(TP &tp, double *lds, const Targe
     tp.attach(dst + (mine ? c / sb.m - t_first : 0) * stride, tb);
     return mine ? c : n;
 }
+// The BatchBlock build: lane threadIdx.x of chunk l of target t owns chain t m + l kBlock + threadIdx.x if that is one of t's,
+// else none (n)
+__device__ __forceinline__ int32_t batch_lane_chain(const BatchBlock &bb, int32_t n)
+{
+    const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
+    const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;
+    return (id < ((int64_t)t + 1) * bb.m && id < (int64_t)n) ? (int32_t)id : n;
+}
+// What fast_kernel and screened_kernel stage before their first __syncthreads(): the target's `rows` doubles (LOG2: the
+// screen's rows with their log2 copies, gsss_screen.h; a batch build: its workgroup's member or members) and the draw tables
+// behind them.  Returns the lane's chain in the shared batch build (stage_shared), else 0.
+template <bool LOG2, class TP, class... BB>
+__device__ __forceinline__ int32_t stage_lane_kernel(TP &tp, double *lds, TargetBlock &tb, int32_t n, size_t rows, fm::Tables &tab,
+                                                     const BB &...batch)
+{
+    constexpr bool kShared = kIsBatchShared<BB...>;
+    int32_t shared_id = 0;
+    if constexpr (kShared) {
+        shared_id = stage_shared(tp, lds, tb, first_of(batch...), n);
+    } else {
+        if constexpr (sizeof...(BB) > 0) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
+        if constexpr (LOG2)
+            tp.stage_log2(lds, tb);
+        else
+            tp.stage(lds, tb);
+    }
+    tab = stage_tables(kShared ? lds : lds + rows);
+    return shared_id;
+}
 
 // NUMPY: the draws come from numpy's own PCG64 / ziggurat stream (rng_state, NumpyDraws) instead of the replay buffer, at
 // the replay path's consumption points -- the reference's own order, a uniform per try that is made and none for one that is
@@ -711,14 +764,8 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
     extern __shared__ __attribute__((aligned(16))) double lds[];
     TP tp;
     constexpr bool kShared = kIsBatchShared<BB...>;  // (BatchShared in BatchBlock's place: stage_shared above)
-    [[maybe_unused]] int32_t shared_id = 0;
-    if constexpr (kShared) {
-        shared_id = stage_shared(tp, lds, tb, first_of(batch...), (int32_t)a.n_chains);
-    } else {
-        if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
-        tp.stage(lds, tb);
-    }
-    const fm::Tables tab = stage_tables(kShared ? lds : lds + TP::lds_doubles());
+    fm::Tables tab;
+    [[maybe_unused]] const int32_t shared_id = stage_lane_kernel<false>(tp, lds, tb, (int32_t)a.n_chains, TP::lds_doubles(), tab, batch...);
     // word w of this lane's parked chain lives at park[w * kBlock]: conflict-free across lanes
     unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + TP::lds_doubles() + kTabLds) + threadIdx.x;
     NumpyDraws<V> nd;
@@ -740,11 +787,8 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
                          : (int32_t)blockIdx.x * kPerBlock + (int32_t)threadIdx.x;
     if constexpr (kShared) {  // lane threadIdx.x of the workgroup's run of consecutive chains, or none (n)
         id0 = shared_id;
-    } else if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
-        const BatchBlock &bb = first_of(batch...);
-        const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
-        const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;
-        id0 = (id < ((int64_t)t + 1) * bb.m && id < (int64_t)n) ? (int32_t)id : n;
+    } else if constexpr (BATCH) {
+        id0 = batch_lane_chain(first_of(batch...), n);
     }
     const int32_t id1 = (BATCH || spread) ? n : id0 + kBlock;
 
@@ -768,12 +812,7 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
         }
         return a.replay[(size_t)chain_id() * a.replay_stride + cur.cursor++];
     };
-
-    auto count_tries = [&]() {
-        const uint32_t sum = cur.n_try + (uint32_t)cur.t;
-        if (sum < cur.n_try) cur.err |= GSSS_CHAIN_COUNTER_SATURATED;  // > 2^32-1 proposals in one launch
-        cur.n_try = sum < cur.n_try ? 0xFFFFFFFFu : sum;
-    };
+    auto count_tries = [&]() { gsss::count_tries(cur); };
     auto init = [&]() {
         const int32_t c = chain_id();
         const bool valid = c < n;
@@ -843,17 +882,9 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
             for (int j = 0; j < D; ++j) cur.u[j] *= rnw;
         }
         const double lvl0 = tp.make(cur.cf, cur.x, cur.u, cur.lvl, cur.steps_done == 0);
-        bool finite;
-        if constexpr (kPowerThreshold<TP>) {
-            cur.thr = TP::threshold(lvl0, u_thr);
-            finite = lvl0 > 0.0 && lvl0 < INFINITY;
-        } else if (TP::kLinear) {
-            cur.thr = lvl0 * u_thr;
-            finite = lvl0 > 0.0 && lvl0 < INFINITY;
-        } else {
-            cur.thr = lvl0 + fm::log_fast(u_thr);
-            finite = lvl0 > -INFINITY && lvl0 < INFINITY;
-        }
+        const SliceThreshold th = slice_threshold<TP>(lvl0, u_thr);
+        cur.thr = th.thr;
+        const bool finite = th.finite;
         if (shrink) {
             cur.hi = kTwoPi * u_th0;
             cur.lo = cur.hi - kTwoPi;
@@ -1479,18 +1510,9 @@ __global__ void __launch_bounds__(kBlock, V::N >= 16 ? 2 : 4) coopfast_kernel(Ta
             lvl0 = tp.level_distributed(my, g, 1.0, 0.0);
         else
             lvl0 = tp.level0(cf, lvl, s == 0);
-        double thr;
-        bool finite;
-        if constexpr (kPowerThreshold<TP>) {
-            thr = TP::threshold(lvl0, u_thr);
-            finite = lvl0 > 0.0 && lvl0 < INFINITY;
-        } else if (TP::kLinear) {
-            thr = lvl0 * u_thr;
-            finite = lvl0 > 0.0 && lvl0 < INFINITY;
-        } else {
-            thr = lvl0 + fm::log_fast(u_thr);
-            finite = lvl0 > -INFINITY && lvl0 < INFINITY;
-        }
+        const SliceThreshold th = slice_threshold<TP>(lvl0, u_thr);
+        const double thr = th.thr;
+        const bool finite = th.finite;
         if (!finite || !x_ok) {
             err |= GSSS_CHAIN_NONFINITE;
             break;
@@ -1751,18 +1773,9 @@ __global__ void __launch_bounds__(kBlock) wave_kernel(TargetBlock tb, RunBlock a
             for (int j = 0; j < D; ++j) u[j] *= rnw;
         }
         const double lvl0 = tp.make(cf, x, u, lvl, s == 0);
-        double thr;
-        bool finite;
-        if constexpr (kPowerThreshold<TP>) {
-            thr = TP::threshold(lvl0, u_thr);
-            finite = lvl0 > 0.0 && lvl0 < INFINITY;
-        } else if (TP::kLinear) {
-            thr = lvl0 * u_thr;
-            finite = lvl0 > 0.0 && lvl0 < INFINITY;
-        } else {
-            thr = lvl0 + fm::log_fast(u_thr);
-            finite = lvl0 > -INFINITY && lvl0 < INFINITY;
-        }
+        const SliceThreshold th = slice_threshold<TP>(lvl0, u_thr);
+        const double thr = th.thr;
+        const bool finite = th.finite;
         if (!finite || !x_ok) {
             err |= GSSS_CHAIN_NONFINITE;
             break;

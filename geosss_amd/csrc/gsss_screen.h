@@ -905,17 +905,8 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     constexpr bool kShared = kIsBatchShared<BB...>;  // (BatchShared in BatchBlock's place: stage_shared, gsss_fast.h)
     constexpr bool kLog2 = !BATCH && screen_log2_rows<TP>::value;  // the rows once more in log2 units, behind the unscaled ones
     constexpr size_t kRows = BATCH ? TP::lds_doubles() : screen_row_doubles<TP>();
-    [[maybe_unused]] int32_t shared_id = 0;
-    if constexpr (kShared) {
-        shared_id = stage_shared(tp, lds, tb, first_of(batch...), (int32_t)a.n_chains);
-    } else {
-        if constexpr (BATCH) tb.blob += (int64_t)(blockIdx.x / (uint32_t)first_of(batch...).chunks) * first_of(batch...).stride;
-        if constexpr (kLog2)
-            tp.stage_log2(lds, tb);
-        else
-            tp.stage(lds, tb);
-    }
-    const fm::Tables tab = stage_tables(kShared ? lds : lds + kRows);
+    fm::Tables tab;
+    [[maybe_unused]] const int32_t shared_id = stage_lane_kernel<kLog2>(tp, lds, tb, (int32_t)a.n_chains, kRows, tab, batch...);
     unsigned long long *park = reinterpret_cast<unsigned long long *>(lds + kRows + kTabLds) + threadIdx.x;
     NumpyDraws<V> nd;
     if constexpr (NUMPY) nd.stage(lds + kRows + kTabLds);
@@ -964,11 +955,8 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     int32_t id0 = (int32_t)chunk * (a.one_per_lane ? kBlock : kPerBlock) + (int32_t)threadIdx.x;
     if constexpr (kShared) {  // lane threadIdx.x of the workgroup's run of consecutive chains, or none (n)
         id0 = shared_id;
-    } else if constexpr (BATCH) {  // lane threadIdx.x of chunk l of target t: chain t m + l kBlock + threadIdx.x if that is one of t's, else none (n)
-        const BatchBlock &bb = first_of(batch...);
-        const uint32_t t = blockIdx.x / (uint32_t)bb.chunks, l = blockIdx.x - t * (uint32_t)bb.chunks;
-        const int64_t id = (int64_t)t * bb.m + (int64_t)l * kBlock + (int64_t)threadIdx.x;
-        id0 = (id < ((int64_t)t + 1) * bb.m && id < (int64_t)n) ? (int32_t)id : n;
+    } else if constexpr (BATCH) {
+        id0 = batch_lane_chain(first_of(batch...), n);
     }
     const int32_t id1 = a.one_per_lane ? n : id0 + kBlock;
 
@@ -996,11 +984,7 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         }
         return a.replay[(size_t)chain_id() * a.replay_stride + cur.cursor++];
     };
-    auto count_tries = [&]() {
-        const uint32_t sum = cur.n_try + (uint32_t)cur.t;
-        if (sum < cur.n_try) cur.err |= GSSS_CHAIN_COUNTER_SATURATED;
-        cur.n_try = sum < cur.n_try ? 0xFFFFFFFFu : sum;
-    };
+    auto count_tries = [&]() { gsss::count_tries(cur); };
     auto needs_service = [](int32_t st) { return st == kPending || is_final(st); };
 
     auto init = [&]() {

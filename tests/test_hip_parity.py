@@ -669,6 +669,64 @@ def test_numpy_stream_lane_kernel(gs, oracle, name, n_chains, sampler):
     assert np.max(np.abs(more - want2["samples"][:, n_steps:])) < TOL
 
 
+@pytest.mark.parametrize("name", ["vmfmix_readme", "vmfmix_d4_k4_weighted", "vmfmix_d10_k5_kappa100"])  # d = 3, 4, 10
+@pytest.mark.parametrize("sampler", ["shrink", "reject"])
+def test_numpy_stream_with_running_statistics(gs, oracle, name, sampler):
+    """numpy's stream WITH running statistics -- builds of their own: screened_kernel<.., REPLAY, STATS, .., NUMPY>, the
+    all-double fast_kernel<.., REPLAY, STATS, NUMPY> (screen=False) and wave_kernel<.., NUMPY, STATS> (spread) -- against the
+    oracle's numpy stream, as test_numpy_stream_lane_kernel holds the builds without statistics: states at 1e-10, tries
+    exact (the rows are held to the oracle; the mean the kernels accumulate is then held to those rows).  513 chains: a full workgroup and one of a
+    single lane; 8 steps, every second kept, in two launches of 4."""
+    import torch
+    z = golden(f"traj_{name}.npz")
+    pdf, tgt = product_target(z), oracle.Target.from_fixture(z)
+    d, n = len(z["x0"]), 513
+    x0 = oracle.sample_sphere(3, n, d)
+    kind = oracle.REJECT if sampler == "reject" else oracle.SHRINK
+    want = oracle.run(tgt, x0, 8, numpy_seed=list(np.random.SeedSequence(77).spawn(n)), sampler=kind)
+    cls = gs.RejectionSphericalSliceSampler if sampler == "reject" else gs.ShrinkageSphericalSliceSampler
+    for kernel, kw in (("screened_kernel", dict(placement="packed")), ("fast_kernel", dict(placement="packed", screen=False)),
+                       ("wave_kernel", dict(placement="spread"))):
+        s = cls(pdf, x0, np.random.SeedSequence(77), rng="numpy", mode="fast", **kw).enable_stats(lags=0)
+        chosen = s._lib.gsss_kernel_name(s._target_dev.handle, 1, 0 if kw.get("screen", True) else 100, s._placement).decode()
+        assert chosen.startswith(kernel), (kw, chosen)
+        kept = torch.cat([s.advance(4, thin=2), s.advance(4, thin=2)]).permute(2, 0, 1)  # (chains, draws, dims)
+        assert np.max(np.abs(kept.cpu().numpy() - want["samples"][:, 1::2])) < TOL, kw
+        assert np.array_equal(s.n_tries_per_chain, want["n_tries"]), kw
+        r = s.stats()
+        assert torch.equal(r["n"], torch.full((n,), 4.0, dtype=torch.float64, device=kept.device)), kw
+        assert torch.allclose(r["mean"], kept.mean(1), rtol=0, atol=1e-13), kw
+
+
+@pytest.mark.parametrize("name", ["vmfmix_readme", "vmfmix_d4_k4_weighted", "vmfmix_d10_k5_kappa100"])  # d = 3, 4, 10
+@pytest.mark.parametrize("sampler", ["shrink", "reject"])
+def test_all_double_lane_kernel_with_running_statistics(gs, oracle, name, sampler):
+    """fast_kernel<.., STATS> on the library stream (screen=False with running statistics: a build of its own, which parks a
+    second chain per lane) against the oracle's Philox chains, as test_philox_stream_matches_oracle holds the plain builds:
+    states at 1e-10, tries and rejections exact; the mean the kernel accumulates is then held to the rows it kept.  d = 3
+    (the tangent is drawn directly), d = 4 (projected), d = 10 (the last dimension that parks); 513 chains: a workgroup with
+    both slots of every lane taken and one with a single chain; 8 steps, every second kept, in two launches of 4."""
+    import torch
+    z = golden(f"traj_{name}.npz")
+    pdf, tgt = product_target(z), oracle.Target.from_fixture(z)
+    d, n = len(z["x0"]), 513
+    x0 = oracle.sample_sphere(11, n, d, chain_offset=1000)
+    kind = oracle.REJECT if sampler == "reject" else oracle.SHRINK
+    want = oracle.run(tgt, x0, 8, seed=2024, chain_offset=1000, step_offset=7, sampler=kind, n_threads=8)
+    cls = gs.RejectionSphericalSliceSampler if sampler == "reject" else gs.ShrinkageSphericalSliceSampler
+    s = cls(pdf, x0, seed=2024, chain_offset=1000, step_offset=7, mode="fast", placement="packed", screen=False).enable_stats(lags=0)
+    chosen = s._lib.gsss_kernel_name(s._target_dev.handle, 1, 100, 1).decode()
+    assert chosen.startswith("fast_kernel"), chosen
+    kept = torch.cat([s.advance(4, thin=2), s.advance(4, thin=2)]).permute(2, 0, 1)  # (chains, draws, dims)
+    assert np.all(s.errors == 0) and np.all(want["err"] == 0)
+    assert np.max(np.abs(kept.cpu().numpy() - want["samples"][:, 1::2])) < TOL
+    assert np.array_equal(s.n_tries_per_chain, want["n_tries"])
+    assert np.array_equal(s.n_reject_per_chain, want["n_reject"])
+    r = s.stats()
+    assert torch.equal(r["n"], torch.full((n,), 4.0, dtype=torch.float64, device=kept.device))
+    assert torch.allclose(r["mean"], kept.mean(1), rtol=0, atol=1e-13)
+
+
 def test_edge_shapes(gs):
     """Empty ensemble, one chain, one draw, ragged block tails, zero steps."""
     z = golden("traj_vmfmix_readme.npz")

@@ -6,8 +6,14 @@ objects with llvm-objdump and compares the function bodies by their mangled name
 build.sources().  Reported per unit and for the union of the kernels over all units (a kernel may move between units; in the
 union a name counts as different if any of its bodies differs).  Normalised: the literal that follows s_getpc_b64 (the
 pc-relative address of a table) and the padding behind a function depend on where the object was laid out, not on the kernel.  Up to 16 compilations run in
-parallel (--jobs)."""
-import argparse, concurrent.futures as cf, os, re, subprocess, sys, tempfile
+parallel (--jobs).  A body that differs is also compared by its count per opcode with s_nop and s_waitcnt left out: equal
+counts mean the same work in another order ("scheduling only"); the exit status is 0 if no kernel differs by more than that
+(and, with --resources, in no figure), else 1.
+    python tools/compare_kernels.py --resources <other tree> [units ...]
+compares each kernel's resource figures as well, in the code object's metadata: VGPRs (all of them; AGPRs are among them and
+also given alone), SGPRs, spills, scratch and static LDS bytes, and the wavefronts per SIMD that the registers allow (512 / VGPRs
+in blocks of 8, at most 8: derived, not stored)."""
+import argparse, collections, concurrent.futures as cf, os, re, subprocess, sys, tempfile
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
@@ -16,7 +22,32 @@ from geosss_amd import build
 LLVM = os.path.join(os.path.dirname(os.path.realpath(build.hipcc())), "..", "lib", "llvm", "bin")
 
 
-def functions(tree, unit, tmp, tag):
+RESOURCE_KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+                 "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def resources(elf):
+    """{kernel: its figures} from the AMDGPU metadata note (a kernel's entry starts at the list's own indent; a key the entry
+    does not carry counts as -1)."""
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", elf], check=True, capture_output=True, text=True).stdout
+    d = {}
+    for entry in re.split(r"^  - (?=\.)", notes, flags=re.M)[1:]:
+        name = re.search(r"^\s*\.name:\s*(\S+)", entry, re.M)
+        if not name:
+            continue
+        found = (re.search(rf"^\s*\.{k}:\s*(\d+)", entry, re.M) for k in RESOURCE_KEYS)
+        fig = tuple(int(m.group(1)) if m else -1 for m in found)
+        d[name.group(1)] = fig + (min(8, 512 // max(8, -(-fig[0] // 8) * 8)),)
+    return d
+
+
+def scheduling_only(x, y):
+    def count(body):
+        return collections.Counter(i.split()[0] for i in body if not i.startswith(("s_nop", "s_waitcnt")))
+    return count(x) == count(y)
+
+
+def functions(tree, unit, tmp, tag, want_resources=False):
     co, elf = os.path.join(tmp, f"{tag}.co"), os.path.join(tmp, f"{tag}.elf")
     subprocess.run([build.hipcc(), *build.CXXFLAGS, *build.source_flags(unit), "--cuda-device-only", "-c",
                     os.path.join(tree, "geosss_amd", "csrc", unit), "-o", co], check=True, capture_output=True)
@@ -36,26 +67,44 @@ def functions(tree, unit, tmp, tag):
             if since_pc in (1, 2) and ins.startswith(("s_add_u32", "s_addc_u32")):
                 ins = re.sub(r"0x[0-9a-f]+$", "<pcrel>", ins)
             d[cur].append(ins)
-    return d
+    return d, (resources(elf) if want_resources else {})
 
 
-def report(label, a, b):
-    """a, b: {kernel: body} there and here.  Prints one line (and the offenders), returns how many differ or are missing."""
+def report(label, a, b, sched=None):
+    """a, b: {kernel: body} there and here (resources: its figures; the union: the set of its bodies or figures).  `sched`:
+    {kernel: all its differing bodies were scheduling only}, filled from the units' bodies and read for the union.  Prints one
+    line and the offenders; returns how many are missing, new or differ by more than their schedule."""
     same = [k for k in a if a[k] == b.get(k)]
     diff = [k for k in a if k in b and a[k] != b[k]]
     gone = [k for k in a if k not in b]
     new = [k for k in b if k not in a]
-    print(f"{label}: {len(a)} kernels there, {len(b)} here; identical bodies: {len(same)} ({sum(len(a[k]) for k in same)} "
-          f"instructions), different: {len(diff)}, missing here: {len(gone)}, new here: {len(new)}")
+    print(f"{label}: {len(a)} kernels there, {len(b)} here; identical: {len(same)}, different: {len(diff)}, "
+          f"missing here: {len(gone)}, new here: {len(new)}")
+    worse = 0
     for k in diff + gone + new:
-        print("   ", "different" if k in diff else "missing  " if k in gone else "new      ", k)
-    return len(diff) + len(gone) + len(new)
+        note, only = "", False
+        if k in diff and isinstance(a[k], list):  # one unit's bodies
+            only = scheduling_only(a[k], b[k])
+            if sched is not None:
+                sched[k] = only and sched.get(k, True)
+            note = f"  [{len(a[k])} -> {len(b[k])} instructions, " + ("scheduling only]" if only else "OTHER OPCODE COUNTS]")
+        elif k in diff and isinstance(a[k], tuple):  # one unit's resource figures
+            note = f"  {a[k]} -> {b[k]}"
+        elif k in diff and sched is not None and k in sched:  # the union of the bodies
+            only = sched[k]
+            note = "  [scheduling only]" if only else "  [OTHER OPCODE COUNTS]"
+        worse += not only
+        print("   ", "different" if k in diff else "missing  " if k in gone else "new      ", k + note)
+    if diff:
+        print(f"    of the different: scheduling only {len(diff) + len(gone) + len(new) - worse}, more than that {worse - len(gone) - len(new)}")
+    return worse
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("other", help="the other source tree")
     ap.add_argument("units", nargs="*", help="translation units (default: every unit of the build)")
+    ap.add_argument("--resources", action="store_true", help="also compare resource figures " + str(RESOURCE_KEYS + ("waves/SIMD",)))
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 1))
     a = ap.parse_args()
     units = a.units or build.sources()
@@ -65,19 +114,22 @@ def main():
         def side(tree, tag):
             def one(unit):
                 if not os.path.exists(os.path.join(tree, "geosss_amd", "csrc", unit)):
-                    return {}
-                return functions(tree, unit, tmp, f"{tag}_{unit}")
+                    return {}, {}
+                return functions(tree, unit, tmp, f"{tag}_{unit}", a.resources)
             return one
         there = list(ex.map(side(a.other, "other"), units))
         here = list(ex.map(side(HERE, "this"), units))
-    union_there, union_here = {}, {}
-    for union, per_unit in ((union_there, there), (union_here, here)):
-        for fns in per_unit:
-            for k, body in fns.items():  # one name, several bodies (weak copies in several units): all of them
-                union.setdefault(k, set()).add(tuple(body))
-    for unit, x, y in zip(units, there, here):
-        report(unit, x, y)
-    bad = report("union of all units", union_there, union_here)
+    bad = 0
+    for what in range(2 if a.resources else 1):  # the bodies, then the resource figures
+        union_there, union_here, sched = {}, {}, ({} if what == 0 else None)
+        for union, per_unit in ((union_there, there), (union_here, here)):
+            for fns in per_unit:
+                for k, body in fns[what].items():  # one name, several bodies (weak copies in several units): all of them
+                    union.setdefault(k, set()).add(tuple(body))
+        for unit, x, y in zip(units, there, here):
+            report(unit + (" resources" if what else ""), x[what], y[what], sched)
+        bad += report("union of all units" + (" resources" if what else ""), union_there, union_here, sched)
+    # exit status: 0 if every kernel is identical or differs in its schedule only (and, with --resources, in no figure)
     sys.exit(1 if bad else 0)
 
 
