@@ -14,6 +14,7 @@
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
+#include "gsss_autocov.h"
 #include "gsss_moments.h"
 #include "gsss_user_target.h"
 
@@ -1450,6 +1451,50 @@ int gsss_scalar_moments(const double *values_dev, int64_t n_rows, int64_t n_chai
     if (!guard.ok) return GSSS_E_HIP;
     // [n_rows][1][n_chains] through the any-d diagonal kernel: acc rows count, sum v, sum v^2
     return launch_target_moments(values_dev, n_rows, n_chains, 1, 0, chains_per_target, true, acc_dev, chain_sum_dev,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int64_t gsss_autocov_rows(int32_t d, int32_t n_lags)
+{
+    if (d < 1 || n_lags < 1) return GSSS_E_INVALID;
+    if (n_lags > kAutocovMaxLags) return GSSS_E_UNSUPPORTED;
+    return (int64_t)d * autocov_sums(n_lags);
+}
+
+int gsss_target_autocov(const double *ring_dev, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist, int64_t n_chains,
+                        int32_t d, int64_t chains_per_target, int32_t n_lags, double *acc_dev, int device, void *stream)
+{
+    if (d < 1 || n_lags < 1) {
+        set_error("gsss_target_autocov: need d >= 1 and n_lags >= 1 (d = %d, n_lags = %d)", d, n_lags);
+        return GSSS_E_INVALID;
+    }
+    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
+        set_error("gsss_target_autocov: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
+                  (long long)chains_per_target);
+        return GSSS_E_INVALID;
+    }
+    if (ring_rows < 0 || first_row < 0 || n_rows < 0 || n_hist < 0 || n_rows > ring_rows || first_row > ring_rows - n_rows) {
+        set_error("gsss_target_autocov: the rows %lld .. + %lld do not lie in a ring of %lld rows", (long long)first_row,
+                  (long long)n_rows, (long long)ring_rows);
+        return GSSS_E_INVALID;
+    }
+    if (n_hist > n_lags || n_hist > ring_rows - n_rows) {
+        set_error("gsss_target_autocov: n_hist (%lld) exceeds n_lags (%d) or the ring's rows outside the block (%lld)",
+                  (long long)n_hist, n_lags, (long long)(ring_rows - n_rows));
+        return GSSS_E_INVALID;
+    }
+    if (n_lags > kAutocovMaxLags) {
+        set_error("gsss_target_autocov: at most %d lags are kept (n_lags = %d)", kAutocovMaxLags, n_lags);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    if (!ring_dev || !acc_dev) {
+        set_error("gsss_target_autocov: %s is null", ring_dev ? "acc_dev" : "ring_dev");
+        return GSSS_E_INVALID;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    return launch_target_autocov(ring_dev, ring_rows, first_row, n_rows, n_hist, n_chains, d, chains_per_target, n_lags, acc_dev,
                                  static_cast<hipStream_t>(stream));
 }
 

@@ -16,7 +16,7 @@ import torch
 
 __all__ = ["acf", "acf_fft", "IAT", "n_eff", "distance", "hopping_frequency", "mode_occupancy", "mode_kl", "from_running",
            "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments",
-           "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw"]
+           "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw", "target_autocov", "from_target_autocov"]
 
 
 def _t(x):
@@ -475,9 +475,93 @@ def from_scalar_moments(acc, chain_sum, chains_per_target):
             "rhat": torch.sqrt((within + between) / (within * (r / (r - 1)))), "ess_between": (within + between) / between}
 
 
+def target_autocov(x, chains_per_target, lags, *, acc=None, hist=None):
+    """Per-target lagged products of a block of draws on the device, in one pass and without atomics (gsss_target_autocov,
+    include/gsss.h).
+
+    x: a CUDA float64 tensor, component-major (R, d, n) -- what `advance(..., thin=t)` returns -- or (R, n) for a scalar series.
+    Target t owns the chains [t m, (t + 1) m), m = chains_per_target.  Returns the accumulator (M, d, L + 1, 3), M = n / m,
+    L = lags: for every target, series j and lag l the sums over the target's chains and the rows r of
+    C = x_{r,j} x_{r-l,j}, P = x_{r,j} and Q = x_{r-l,j}, a pair counting where r - l is a row of x or of `hist`.  `hist`: the up to
+    `lags` rows that precede x (same trailing shape, oldest first), for a caller who streams a series block by block; `acc`
+    continues an earlier accumulator (added to, returned).  -> `from_target_autocov`."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64 or x.ndim not in (2, 3):
+        raise ValueError("x must be a CUDA float64 tensor (R, d, n), or (R, n) for a scalar series")
+    if x.ndim == 2:
+        x = x[:, None, :]
+    R, d, n = (int(v) for v in x.shape)
+    m, L = int(chains_per_target), int(lags)
+    if m < 1 or n % m:
+        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+    if not 1 <= L <= 64:
+        raise ValueError(f"lags must be 1 .. 64 (got {lags})")
+    M, h = n // m, 0
+    if hist is not None:
+        if isinstance(hist, torch.Tensor) and hist.ndim == 2:
+            hist = hist[:, None, :]
+        if (not isinstance(hist, torch.Tensor) or hist.ndim != 3 or tuple(hist.shape[1:]) != (d, n) or hist.dtype != torch.float64
+                or hist.device != x.device or hist.shape[0] > L):
+            raise ValueError(f"hist must be a float64 tensor of at most {L} rows shaped like the rows of x, on the device of x")
+        h = int(hist.shape[0])
+    if acc is None:
+        acc = torch.zeros((M, d, L + 1, 3), dtype=torch.float64, device=x.device)
+    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (M, d, L + 1, 3) or acc.dtype != torch.float64
+          or acc.device != x.device or not acc.is_contiguous()):
+        raise ValueError(f"acc must be a contiguous float64 tensor ({M}, {d}, {L + 1}, 3) on the device of x")
+    if R == 0 or n == 0:
+        return acc
+    ring = torch.cat([x, hist]) if h else x.contiguous()     # the rows before row 0 of a ring are its last
+    _autocov_fold(ring, 0, R, h, m, L, acc)
+    return acc
+
+
+def _autocov_fold(ring, first_row, n_rows, n_hist, m, lags, acc):
+    """gsss_target_autocov on the rows first_row .. + n_rows of a contiguous ring (rows, d, n)."""
+    from . import _lib
+    from .sphere import current_stream_ptr
+    rows, d, n = (int(v) for v in ring.shape)
+    dev = ring.device.index if ring.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsss_target_autocov(ring.data_ptr(), rows, first_row, n_rows, n_hist, n, d, m, lags, acc.data_ptr(),
+                                                   dev, current_stream_ptr(dev)))
+
+
+def from_target_autocov(acov, chains_per_target, n):
+    """Per-target within-chain autocorrelation from the accumulators of `target_autocov` / `Sampler.summarize(lags=L)`:
+    acov (M, d, L + 1, 3) = (C, P, Q) per target, series and lag, m = chains_per_target chains of n draws each (n: a number or
+    one per target).  With the pooled mean mu = P_0 / (m n) and k_l = m (n - l) pairs,
+
+        cov_l = (C_l - mu (P_l + Q_l)) / k_l + mu^2,      acf_l = cov_l / cov_0      (M, d, L + 1),
+
+    the direct estimator of `acf` (utils.py:96-110) centred on the target's pooled mean: at m = 1 it is
+    `acf(series, n_max=L + 1)`.  iat (M, d): `iat_from_acf` (the pair-sum heuristic of utils.py:119-131); ess_within = m n / iat;
+    iat_truncated: no adjacent pair of the L lags went negative, the sum stopped at the window's end and the IAT is a LOWER
+    bound (raise `lags` or thin more).  CPU or CUDA tensors.  ValueError where n <= L."""
+    acov = _t(acov).to(torch.float64)
+    if acov.ndim != 4 or acov.shape[-1] != 3 or acov.shape[2] < 2:
+        raise ValueError("acov must be (M, d, L + 1, 3)")
+    m, L = int(chains_per_target), int(acov.shape[2]) - 1
+    n = torch.as_tensor(n, dtype=torch.float64, device=acov.device).reshape(-1, 1, 1)
+    if bool((n <= L).any()):
+        raise ValueError("the autocorrelation needs more than `lags` retained draws per chain")
+    c, p, q = acov[..., 0], acov[..., 1], acov[..., 2]
+    mu = p[..., :1] / (m * n)
+    k = m * (n - torch.arange(L + 1, dtype=torch.float64, device=acov.device))
+    cov = (c - mu * (p + q)) / k + mu * mu
+    ac = cov / cov[..., :1]
+    iat = iat_from_acf(ac)
+    return {"acf": ac, "iat": iat, "ess_within": m * n.reshape(-1, 1) / iat, "iat_truncated": ~pair_sum_went_negative(ac)}
+
+
 class TargetMoments:
     """What `Sampler.summarize` returns: the per-target accumulators of a run (`acc` (M, rows), `chain_sum` (d, n), device
     tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`.
+
+    With `summarize(lags=L)` also the lagged products of every coordinate: `lags` = L, `acov` (M, d, L + 1, 3) (see
+    `target_autocov`) and `hist`, the last min(L, draws) retained rows (h, d, n), from which into= goes on; with log_prob=True
+    `lp_acov` (M, 1, L + 1, 3) and `lp_hist` (h, 1, n) for the log-density series.  stats() then adds acf, iat, ess_within,
+    iat_truncated (`from_target_autocov`) and lp_acf, lp_iat, lp_ess_within, lp_iat_truncated.
+
 
     With `summarize(log_prob=True)` also the log-density trace: `lp_acc` (M, 3) -- count, sum, sum of squares of log_prob over
     the target's draws --, `lp_chain_sum` (n,), and the best draw seen per target, `lp_best` (M,) and `x_best` (M, d): the maximum
@@ -489,6 +573,7 @@ class TargetMoments:
         self.acc, self.chain_sum, self.d = acc, chain_sum, int(d)
         self.chains_per_target, self.second_moment = int(chains_per_target), bool(second_moment)
         self.lp_acc, self.lp_chain_sum, self.lp_best, self.x_best = lp_acc, lp_chain_sum, lp_best, x_best
+        self.lags, self.acov, self.hist, self.lp_acov, self.lp_hist = None, None, None, None, None
 
     @property
     def n_targets(self):
@@ -510,6 +595,12 @@ class TargetMoments:
             out.update(lp_mean=lp["mean"], lp_var=lp["var"], lp_rhat=lp["rhat"], lp_ess_between=lp["ess_between"])
         if self.lp_best is not None:
             out.update(lp_best=self.lp_best, x_best=self.x_best)
+        if self.acov is not None:
+            per_chain = self.acc[:, 0] / self.chains_per_target
+            out.update(from_target_autocov(self.acov, self.chains_per_target, per_chain))
+            if self.lp_acov is not None:
+                lp = from_target_autocov(self.lp_acov, self.chains_per_target, per_chain)
+                out.update({"lp_" + key: val[:, 0] for key, val in lp.items()})
         return out
 
 

@@ -619,7 +619,7 @@ class RejectionSphericalSliceSampler:
         return out[0] if self._single else out
 
     def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None,
-                  log_prob=False):
+                  log_prob=False, lags=None):
         """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
         would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
         windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
@@ -637,7 +637,21 @@ class RejectionSphericalSliceSampler:
         `lp_chain_sum` (gsss_scalar_moments) and into the running best draw per target, `lp_best` / `x_best` -- the MAP estimate
         among the retained draws; stats() then reports lp_mean, lp_var, lp_rhat, lp_ess_between, lp_best, x_best.  into=
         continues them too (a summary that carries them goes on carrying them); one begun without cannot take them up.  The
-        moments, the chains and the launches of the default are untouched by it."""
+        moments, the chains and the launches of the default are untouched by it.
+
+        lags=L (1 .. 64): also the within-chain autocorrelation of every coordinate, the estimator that needs no more than a few
+        chains per target.  The one reused buffer becomes a ring of L + window rows -- L d n 8 bytes more than the windows need;
+        window=None sizes the whole ring to 256 MiB where that leaves a window row -- into which draw 0 is copied as row 0 and
+        the windows are written one behind the other, cut so that none wraps; every window is folded by gsss_target_autocov
+        beside the moments fold, its L rows of history read where they lie in the ring.  (Every fold reads its L rows of
+        history: where 256 MiB leave windows of a row or two -- 10^6 chains -- pass window=L or more, a ring of 2 L rows, and
+        the lags cost a few ms; DESIGN.md §5.6g has the figures.)  The result carries `acov`
+        (M, d, L + 1, 3) and the ring's last L rows, from which into= goes on; stats() adds acf (M, d, L + 1), iat, ess_within
+        = m n / iat and iat_truncated (diagnostics.from_target_autocov).  With log_prob=True the value buffer becomes a ring too
+        and the log-density series is folded the same way: lp_acf, lp_iat, lp_ess_within, lp_iat_truncated.  n_samples <= L is
+        refused; a summary begun without lags cannot take them up.  The chains, the final state and -- window for window -- the
+        moments are those of the default; where the ring's end cuts a window that the default would not cut, acc and chain_sum
+        may differ from the default's in the last bits (per-window partial sums are added)."""
         from . import diagnostics
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")
@@ -657,6 +671,12 @@ class RejectionSphericalSliceSampler:
         if log_prob and self._batch_m is None:
             raise ValueError("summarize(log_prob=True) evaluates the draws with the batch kernel: wrap the target in a TargetBatch "
                              "of one (TargetBatch([pdf]), chains_per_target = n_chains)")
+        if lags is not None:
+            if not 1 <= int(lags) <= 64:
+                raise ValueError(f"lags must be 1 .. 64 (got {lags})")
+            if into is None and int(n_samples) <= int(lags):
+                raise ValueError(f"the autocorrelation needs more than `lags` retained draws per chain (n_samples = {n_samples}, "
+                                 f"lags = {lags})")
         full, rows = diagnostics._moments_form(d, second_moment if into is None or second_moment is not None else into.second_moment)
         if into is None:
             into = diagnostics.TargetMoments(torch.zeros((n // m, rows), dtype=torch.float64, device=self._tdev),
@@ -666,14 +686,25 @@ class RejectionSphericalSliceSampler:
                 into.lp_chain_sum = torch.zeros(n, dtype=torch.float64, device=self._tdev)
                 into.lp_best = torch.full((n // m,), float("-inf"), dtype=torch.float64, device=self._tdev)
                 into.x_best = torch.zeros((n // m, d), dtype=torch.float64, device=self._tdev)
+            if lags is not None:
+                into.lags = int(lags)
+                into.acov = torch.zeros((n // m, d, into.lags + 1, 3), dtype=torch.float64, device=self._tdev)
+                if log_prob:
+                    into.lp_acov = torch.zeros((n // m, 1, into.lags + 1, 3), dtype=torch.float64, device=self._tdev)
         elif (into.d != d or into.chains_per_target != m or into.second_moment != full or tuple(into.acc.shape) != (n // m, rows)
               or tuple(into.chain_sum.shape) != (d, n)):
             raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
         elif log_prob and into.lp_acc is None:
             raise ValueError("into= was begun without log_prob: its draws so far were not evaluated, so it cannot take log_prob up")
+        elif lags is not None and into.lags != int(lags):
+            raise ValueError("into= was begun without these lags: the lagged products of its draws so far were not kept, so it "
+                             "cannot take them up")
         log_prob = into.lp_acc is not None
+        L = into.lags or 0
         rest = int(n_samples) - 1
-        window = max(1, (256 << 20) // (8 * d * n)) if window is None else int(window)
+        if window is None:                            # (with lags the ring of L + window rows is what stays under 256 MiB)
+            window = max(1, (256 << 20) // (8 * d * n) - L)
+        window = int(window)
         if window < 1:
             raise ValueError("window must be >= 1")
         window = max(1, min(window, rest))
@@ -681,25 +712,54 @@ class RejectionSphericalSliceSampler:
         if burnin:
             self.advance(burnin)
 
-        lp_buf = torch.empty((window, n), dtype=torch.float64, device=self._tdev) if log_prob else None
+        rows = L + window
+        lp_buf = torch.empty((rows, n), dtype=torch.float64, device=self._tdev) if log_prob else None
+        buf = torch.empty((rows, d, n), dtype=torch.float64, device=self._tdev) if rest or L else None
 
-        def fold(x):
+        def fold(x, first=0, hist=0):
+            """x: a window (w, d, n); with lags it is the rows first .. of the ring, behind `hist` rows of history"""
+            w = int(x.shape[0])
+            lp = lp_buf[first:first + w] if log_prob else None
             diagnostics.target_moments(x, m, second_moment=full, acc=into.acc, chain_sum=into.chain_sum)
             if log_prob:
-                x, w = x.contiguous(), int(x.shape[0])
+                x = x.contiguous()
                 with torch.cuda.device(self.device):
                     _lib.check(self._lib.gsss_batch_logprob_draws(self._target_dev.handle, x.data_ptr(), w, n, self.chain_offset // m,
-                                                                  lp_buf.data_ptr(), current_stream_ptr(self.device)))
-                diagnostics.scalar_moments(lp_buf[:w], m, acc=into.lp_acc, chain_sum=into.lp_chain_sum)
-                into.update_best(lp_buf[:w], x)
+                                                                  lp.data_ptr(), current_stream_ptr(self.device)))
+                diagnostics.scalar_moments(lp, m, acc=into.lp_acc, chain_sum=into.lp_chain_sum)
+                into.update_best(lp, x)
+            if L:
+                diagnostics._autocov_fold(buf, first, w, hist, m, L, into.acov)
+                if log_prob:
+                    diagnostics._autocov_fold(lp_buf[:, None, :], first, w, hist, m, L, into.lp_acov)
 
-        fold(self._state[None])                       # draw 0: the state itself is a (1, d, n) window
-        buf = torch.empty((window, d, n), dtype=torch.float64, device=self._tdev) if rest else None
-        done = 0
-        while done < rest:
-            w = min(window, rest - done)
-            fold(self.advance(w * thin, thin=thin, out=buf[:w]))
-            done += w
+        if not L:
+            fold(self._state[None])                   # draw 0: the state itself is a (1, d, n) window
+            done = 0
+            while done < rest:
+                w = min(window, rest - done)
+                fold(self.advance(w * thin, thin=thin, out=buf[:w]))
+                done += w
+        else:
+            # The ring: the rows kept by an earlier call, draw 0, then window after window, none of which wraps; the L rows
+            # before a window (round the ring's end) are the L draws before it, where the kernel reads them.
+            seen = 0 if into.hist is None else int(into.hist.shape[0])
+            if seen:
+                buf[:seen] = into.hist
+                if log_prob:
+                    lp_buf[:seen] = into.lp_hist[:, 0]
+            buf[seen] = self._state
+            fold(buf[seen:seen + 1], seen, seen)
+            pos, seen, done = seen + 1, seen + 1, 0
+            while done < rest:
+                pos %= rows
+                w = min(window, rest - done, rows - pos)
+                fold(self.advance(w * thin, thin=thin, out=buf[pos:pos + w]), pos, min(L, seen))
+                pos, seen, done = pos + w, seen + w, done + w
+            last = (pos - min(L, seen) + torch.arange(min(L, seen), device=self._tdev)) % rows
+            into.hist = buf[last]
+            if log_prob:
+                into.lp_hist = lp_buf[last][:, None, :]
         self._account_calls(self._step - steps0)
         self._check_errors()
         self._sync_rng()

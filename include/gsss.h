@@ -386,6 +386,34 @@ int gsss_batch_logprob_draws(const gsss_target *t, const double *samples_dev, in
 int gsss_scalar_moments(const double *values_dev, int64_t n_rows, int64_t n_chains, int64_t chains_per_target, double *acc_dev,
                         double *chain_sum_dev, int device, void *stream);
 
+/* Per-TARGET lagged products of retained draws, streamed: what the within-chain autocorrelation, its integrated autocorrelation
+ * time and N / IAT need (geosss_amd/diagnostics.py from_target_autocov), for ensembles in which target t owns the chains
+ * [t m, (t + 1) m), m = chains_per_target -- the stats_dev lag rows, which a batch refuses, by a kernel of its own beside the
+ * sampler, so it serves every kernel family, mode and dimension.  The series are the d coordinates of a draw (d >= 1: a scalar
+ * series such as the log-density trace is d = 1).  ring_dev is component-major [ring_rows][d][n_chains], the layout gsss_run writes
+ * to samples_dev.  The block is the rows first_row .. first_row + n_rows - 1 (it does not wrap); the n_hist <= n_lags draws that
+ * precede it are the rows (first_row - 1 - i) mod ring_rows, i = 0 .. n_hist - 1: factors only, never leading terms.  Who holds
+ * all the draws passes ring_rows = n_rows, first_row = 0, n_hist = 0; who streams windows gives the ring n_lags + window rows and
+ * never copies history.
+ * acc_dev [n_chains / m][d][n_lags + 1][3], ADDED to (zero it before the first block): per target t, series j and lag l, over the
+ * target's chains c and the rows r of the block whose partner r - l lies in the block or in its history,
+ *     0   C = sum x_{c,r,j} x_{c,r-l,j}      the lagged products
+ *     1   P = sum x_{c,r,j}                  the sum of the leading factors
+ *     2   Q = sum x_{c,r-l,j}                the sum of the lagging factors
+ * so that successive calls over successive blocks of one series give the sums over the whole series, its ends exact: with
+ * mu = P_0 / (m n) and k_l = m (n - l) pairs, cov_l = (C_l - mu (P_l + Q_l)) / k_l + mu^2 is the direct estimator of
+ * utils.acf (geosss/utils.py:96-110) centred on the target's pooled mean.  gsss_autocov_rows(d, n_lags) = d (n_lags + 1) 3, the
+ * doubles per target.
+ * No floating-point atomics: the order of every sum is fixed by the arguments, so a call gives the same bits every time.
+ * GSSS_E_INVALID: d < 1, m < 1, n_chains no multiple of m, n_lags < 1, a negative count, first_row + n_rows > ring_rows,
+ * n_hist > n_lags or > ring_rows - n_rows, a NULL ring_dev / acc_dev with a non-empty block; GSSS_E_UNSUPPORTED: n_lags > 64
+ * (gsss_autocov_rows returns the same codes) -- all of them before the device is touched.  n_rows = 0 does nothing.  The
+ * reference computes acf / IAT / n_eff on the host from one stored chain (geosss/utils.py:96-134). */
+int64_t gsss_autocov_rows(int32_t d, int32_t n_lags);
+int gsss_target_autocov(const double *ring_dev, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist,
+                        int64_t n_chains, int32_t d, int64_t chains_per_target, int32_t n_lags, double *acc_dev, int device,
+                        void *stream);
+
 /* 1 if gsss_run accepts `mode` for this target's shape (fast mode is built for the shapes listed in
  * geosss_amd/csrc/gsss_fast_*.hip), else 0. */
 int gsss_mode_supported(const gsss_target *t, int32_t mode);
