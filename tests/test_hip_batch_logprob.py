@@ -14,11 +14,10 @@ import pytest
 import torch
 from scipy.special import i0
 
-import layout_cases as lc
-import reference_math as rm
+import batch_layout_cases as bc
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-10
+assert bc.TOL == 1e-10  # the bound of (b)
 U = 2.0 ** -53
 LD = np.longdouble
 README_MUS = 80.0 * np.array([[0.87, -0.37, 0.33], [-0.20, -0.89, -0.40], [0.19, 0.22, -0.96]])
@@ -93,33 +92,8 @@ def _check(gs, case, M, sizes=SIZES, device_tensors=True):
     if case == "bingham_d10_mixed" and M > 1:
         diag = [bool(np.array_equal(p.A, np.diag(np.diag(p.A)))) for p in pdfs]
         assert any(diag) and not all(diag)
-    batch = gs.TargetBatch(pdfs)
-    xs = [_points(case, M, n, d) for n in sizes]
-    got = [(batch.log_prob(x), batch.gradient(x)) for x in xs]
-    if device_tensors:  # device tensors in, device tensors out, the same bits
-        for x, (lp, gr) in zip(xs, got):
-            xt = torch.from_numpy(x).cuda()
-            assert np.array_equal(batch.log_prob(xt).cpu().numpy(), lp) and np.array_equal(batch.gradient(xt).cpu().numpy(), gr)
-    # (a) no member was uploaded for any of it ...
-    assert not any("_targets" in p.__dict__ for p in pdfs), "the batch evaluated a member's own handle"
-    # ... then the members' own values (which upload them) and (b) the independent reference, once for the rows of all sizes:
-    # a point's value does not depend on the rows beside it
-    rows = np.concatenate(xs, axis=1)                                   # (M, sum of sizes, d)
-    own_lp = np.stack([p._log_prob_device(rows[t]) for t, p in enumerate(pdfs)])
-    own_gr = np.stack([p._gradient_device(rows[t]) for t, p in enumerate(pdfs)])
-    ref = [rm.log_prob_and_gradient(p, rows[t]) for t, p in enumerate(pdfs)]
-    at = 0
-    for n, x, (lp, gr) in zip(sizes, xs, got):
-        assert lp.shape == (M, n) and gr.shape == (M, n, d)
-        assert np.array_equal(lp, own_lp[:, at:at + n]), (case, M, n)
-        assert np.array_equal(gr, own_gr[:, at:at + n]), (case, M, n)
-        worst = [0.0, 0.0]
-        for t, p in enumerate(pdfs):
-            worst[0] = max(worst[0], lc.rel(lp[t], ref[t][0][at:at + n]))
-            worst[1] = max(worst[1], lc.gradient_error(p, x[t], gr[t], ref[t][1][at:at + n], d))
-        print(f"{case} M={M} n={n}: log_prob {worst[0]:.1e}, gradient {worst[1]:.1e}")
-        assert worst[0] < TOL and worst[1] < TOL, (case, M, n, worst)
-        at += n
+    # (a) and (b) of the module's docstring: the check the layout sweep shares (tests/batch_layout_cases.py)
+    bc.check_logprob(gs, pdfs, case, sizes, device_tensors=device_tensors, xs=[_points(case, M, n, d) for n in sizes])
 
 
 @pytest.mark.parametrize("M", [1, 3, 6])
@@ -237,7 +211,7 @@ def _x0(d, n, seed=5):
 
 
 def _batch(gs, which):
-    """(members, m, mode): the three batches of tests/test_hip_target_summary.py"""
+    """(members, m, mode): the batches of tests/test_hip_target_summary.py"""
     g = np.random.default_rng(11)
     if which == "bingham_d5_m24":
         return [gs.random_bingham(5, vmax=20.0, vmin=0.0, seed=int(g.integers(1 << 30))) for _ in range(6)], 24, "fast"
@@ -251,6 +225,13 @@ def _batch(gs, which):
     if which == "binghamfisher_d17_m8":
         return [gs.BinghamFisher(gs.random_bingham(17, vmax=20.0, vmin=0.0, seed=int(g.integers(1 << 30))).A,
                                  3.0 * g.standard_normal(17)) for _ in range(4)], 8, "auto"
+    if which == "vmfmix_d130_m7":         # exact mode in a sixty-four-lane layout (coop64x4), a ragged workgroup per target
+        out = []
+        for _ in range(4):
+            mu = g.standard_normal((2, 130))
+            mu *= (10.0 + 30.0 * g.random((2, 1))) / np.linalg.norm(mu, axis=1, keepdims=True)
+            out.append(gs.MixtureModel([gs.VonMisesFisher(v) for v in mu], g.random(2) + 0.5))
+        return out, 7, "auto"
     raise KeyError(which)
 
 
@@ -299,7 +280,7 @@ def _best_is_the_twins(tm, draws, lp, m, what, targets=slice(None)):
         assert np.array_equal(got_x[i], draws[t * m + k % m, k // m]), (what, t)
 
 
-@pytest.mark.parametrize("which", ["bingham_d5_m24", "vmfmix_d3_m256", "binghamfisher_d17_m8"])
+@pytest.mark.parametrize("which", ["bingham_d5_m24", "vmfmix_d3_m256", "binghamfisher_d17_m8", "vmfmix_d130_m7"])
 def test_summarize_with_log_prob(gs, which):
     pdfs, m, mode = _batch(gs, which)
     M, d = len(pdfs), pdfs[0].d

@@ -146,7 +146,17 @@ def _targets(which):
             mu *= (10.0 + 30.0 * g.random((2, 1))) / np.linalg.norm(mu, axis=1, keepdims=True)
             out.append(gs.MixtureModel([gs.VonMisesFisher(v) for v in mu], g.random(2) + 0.5))
         return out, (8 if which == "vmfmix_d3_m8" else 1), "exact"
+    if which == "vmfmix_d130_m7":          # tests/test_hip_target_summary.py's: a sixty-four-lane layout, a ragged workgroup per target
+        out = []
+        for _ in range(4):
+            mu = g.standard_normal((2, 130))
+            mu *= (10.0 + 30.0 * g.random((2, 1))) / np.linalg.norm(mu, axis=1, keepdims=True)
+            out.append(gs.MixtureModel([gs.VonMisesFisher(v) for v in mu], g.random(2) + 0.5))
+        return out, 7, "exact"
     raise KeyError(which)
+
+
+LAGS_OF = {"vmfmix_d130_m7": 4}   # every other case runs LAGS
 
 
 def _sampler(pdfs, m, mode, x0):
@@ -175,8 +185,12 @@ def _acf_within(got, x, m, L, what):
     assert np.all(err <= tol), (what, float(np.max(err / tol)))
 
 
-@pytest.mark.parametrize("which", ["bingham_d5_m16", "vmfmix_d3_m8", "vmfmix_d3_m1"])
+@pytest.mark.parametrize("which", ["bingham_d5_m16", "vmfmix_d3_m8", "vmfmix_d3_m1", "vmfmix_d130_m7"])
 def test_summarize_lags_is_the_stored_run(which):
+    _summarize_lags_is_the_stored_run(which, LAGS_OF.get(which, LAGS))
+
+
+def _summarize_lags_is_the_stored_run(which, LAGS):
     pdfs, m, mode = _targets(which)
     M, d = len(pdfs), pdfs[0].d
     x0 = _x0(d, M * m)

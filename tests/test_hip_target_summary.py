@@ -36,6 +36,13 @@ def _batch(which):
     if which == "binghamfisher_d17_m8":   # no batch fast kernel at d = 17: mode "auto" runs the exact kernels and says so
         return [gs.BinghamFisher(gs.random_bingham(17, vmax=20.0, vmin=0.0, seed=int(g.integers(1 << 30))).A,
                                  3.0 * g.standard_normal(17)) for _ in range(4)], 8, "auto"
+    if which == "vmfmix_d130_m7":         # exact mode in a sixty-four-lane layout (coop64x4), a ragged workgroup per target
+        out = []
+        for _ in range(4):
+            mu = g.standard_normal((2, 130))
+            mu *= (10.0 + 30.0 * g.random((2, 1))) / np.linalg.norm(mu, axis=1, keepdims=True)
+            out.append(gs.MixtureModel([gs.VonMisesFisher(v) for v in mu], g.random(2) + 0.5))
+        return out, 7, "auto"
     raise KeyError(which)
 
 
@@ -69,14 +76,14 @@ def _within(tm, ref, mag, cref, cmag, m, R, what, targets=slice(None)):
     assert np.all(np.abs(cs.astype(np.longdouble) - cref[:, chains]) <= 2 * R * U * cmag[:, chains]), (what, "chain_sum")
 
 
-@pytest.mark.parametrize("which", ["bingham_d5_m24", "vmfmix_d3_m256", "binghamfisher_d17_m8"])
+@pytest.mark.parametrize("which", ["bingham_d5_m24", "vmfmix_d3_m256", "binghamfisher_d17_m8", "vmfmix_d130_m7"])
 def test_summarize_is_the_stored_run_summed(which):
     pdfs, m, mode = _batch(which)
     M, d = len(pdfs), pdfs[0].d
     full = d <= 16
     x0 = _x0(d, M * m)
     twin = _sampler(pdfs, m, mode, x0)
-    assert twin.mode == ("exact" if which == "binghamfisher_d17_m8" else "fast")
+    assert twin.mode == ("exact" if which in ("binghamfisher_d17_m8", "vmfmix_d130_m7") else "fast")
     draws = twin.sample(N_SAMPLES, burnin=BURNIN, thin=THIN, as_tensor=True)          # (n, R, d)
     ref, mag, cref, cmag = _reference(draws.permute(1, 2, 0).cpu().numpy(), m, full)
 
