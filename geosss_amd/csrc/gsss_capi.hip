@@ -1224,6 +1224,11 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
     rb.seed = a->seed;
     rb.chain_offset = a->chain_offset;
     rb.step_offset = a->step_offset;
+    const CounterWords cw = counter_words(a->chain_offset, a->n_chains, a->step_offset, a->n_steps);
+    rb.ctr32 = cw.ok;
+    rb.ctr_chain_lo = cw.chain_lo;
+    rb.ctr_step_lo = cw.step_lo;
+    rb.ctr_c3 = cw.c3;
     rb.sampler = a->sampler;
     rb.max_tries = a->max_tries;
     rb.keep_rows = a->samples_chain_rows;
@@ -1272,6 +1277,10 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
                 set_error("fast mode takes at most 2^31-1 steps / chains per call");
                 return GSSS_E_INVALID;
             }
+            if (a->samples_dev && !kept_rows_fit32(a->samples_chain_rows, a->n_steps, a->thin, t->tb.d)) {
+                set_error("the lane-per-chain kernels keep at most 2^31-1 doubles per chain (samples_chain_rows d) and per call and chain (rows d)");
+                return GSSS_E_INVALID;
+            }
             FastPick pick;
             if (fast_select(fast_ask(t, rb.screen, false), pick) != GSSS_OK) return fast_refused(t);
             return fast_launch(pick, tbb, rb, t->batch, false, st);
@@ -1294,6 +1303,11 @@ int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)
             return GSSS_E_INVALID;
         }
         if (served != GSSS_OK) return fast_refused(t);
+        // (the lane kernels address a kept row in 32 x 32 -> 64 bit arithmetic: kept_row, gsss_device.h)
+        if (pick.lane && a->samples_dev && !kept_rows_fit32(a->samples_chain_rows, a->n_steps, a->thin, t->tb.d)) {
+            set_error("the lane-per-chain kernels keep at most 2^31-1 doubles per chain (samples_chain_rows d) and per call and chain (rows d)");
+            return GSSS_E_INVALID;
+        }
         return fast_launch(pick, t->tb, rb, t->batch, replay, st);
     }
     if (mh) {

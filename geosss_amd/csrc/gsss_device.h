@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/gsss.h"
+#include "gsss_counter_words.h"
 #include "gsss_math.h"
 
 namespace gsss {
@@ -71,6 +72,10 @@ struct RunBlock {
                                // follows a piece table behind dead[] (piece_plan, SliceSched::take_piece; the lane kernels only)
     int32_t sched_first;       // chunks below this one are not sliced: their workgroups (blockIdx < sched_first) run the whole launch
                                // (the lane kernels slice only the last, partial round of their workgroups)
+    // The lane kernels' Philox counters (counter_words, gsss_counter_words.h; filled by gsss_run): ctr32 != 0 while the launch
+    // stays inside one block of 2^32 chain ids and one of 2^32 step ids -- word 3 is ctr_c3, words 1 and 2 are 32-bit sums
+    int32_t ctr32;
+    uint32_t ctr_chain_lo, ctr_step_lo, ctr_c3;
 };
 
 // A batch of targets in one launch (gsss_target_create_batch: M members of one family and shape, their blobs at an equal stride;
@@ -529,6 +534,23 @@ inline SlicePlan plan_partial_round(Kern kern, size_t lds_bytes, const RunBlock 
 __device__ __forceinline__ size_t sample_index(const RunBlock &a, int64_t row, int j, int d, int64_t c)
 {
     return a.keep_rows > 0 ? ((size_t)c * a.keep_rows + row) * d + j : ((size_t)row * d + j) * a.n_chains + c;
+}
+
+// The same address for the lane kernels' keep path (screened_kernel, fast_kernel), whose rows, chains and strides fit 32 bits
+// (gsss_run refuses a fast-mode launch whose keep_rows d or rows d reaches 2^31: kept_rows_fit32): component 0 of the row by ONE
+// widening multiply-add, component j a wave-uniform `step` doubles further -- sample_index() multiplies in 64 bits per component.
+struct KeptRow {
+    double *p;     // component 0
+    int64_t step;  // doubles from a component to the next (wave-uniform)
+};
+__device__ __forceinline__ KeptRow kept_row(const RunBlock &a, int32_t row, int d, int32_t c)
+{
+    const bool chain_major = a.keep_rows > 0;
+    const uint32_t rd = (uint32_t)row * (uint32_t)d;
+    // chain-major: c (keep_rows d) + row d; component-major: (row d) n_chains + c
+    const uint32_t m0 = chain_major ? (uint32_t)c : rd, add = chain_major ? rd : (uint32_t)c;
+    const uint32_t m1 = chain_major ? (uint32_t)a.keep_rows * (uint32_t)d : (uint32_t)a.n_chains;
+    return {a.samples + ((uint64_t)m0 * m1 + add), chain_major ? (int64_t)1 : (int64_t)(uint32_t)a.n_chains};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1094,6 +1116,25 @@ struct PhiloxDraws {
         c1 = (uint32_t)step;
         c3 = chain_hi | ((uint32_t)((step >> 32) & 0xFFFFu) << 16);
         t = 0;
+    }
+    // init + begin_step of the lane kernels: the counter of the launch's chain `chain_local` at its step count `steps_done`.
+    // a.ctr32 is the launch's (a scalar branch): no 64-bit sum, no word put together per draw.
+    __device__ __forceinline__ void init_step(const RunBlock &a, int32_t chain_local, int32_t steps_done, int d_)
+    {
+        if (a.ctr32) {
+            k0 = (uint32_t)a.seed;
+            k1 = (uint32_t)(a.seed >> 32);
+            c1 = a.ctr_step_lo + (uint32_t)steps_done;
+            c2 = a.ctr_chain_lo + (uint32_t)chain_local;
+            c3 = a.ctr_c3;
+            chain_hi = a.ctr_c3 & 0xFFFFu;
+            d = d_;
+            exhausted = false;
+            t = 0;
+        } else {
+            init(a, chain_local, d_);
+            begin_step(a.step_offset + (uint64_t)steps_done);
+        }
     }
     __device__ __forceinline__ void words(uint32_t blk, uint32_t (&w)[4]) const
     {

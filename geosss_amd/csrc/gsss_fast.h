@@ -26,6 +26,8 @@
 #pragma once
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "gsss_device.h"
 #include "gsss_fast_select.h"
 #include "gsss_math.h"
@@ -52,6 +54,10 @@ __device__ __forceinline__ double inv_norm(double s) { return s > 1e-200 ? rsqrt
 template <int D, int KC>
 struct FastVmf {
     static constexpr bool kLinear = true;
+    // The lane kernels of this policy (and of ScreenVmf, which derives from it) shed integer bookkeeping (lean_words below): S^2
+    // with up to 10 terms, where it was measured ahead (README mixture) or level (K = 10) and costs no build a wavefront or
+    // scratch; K = 16 on S^2 spills 4 - 16 bytes more with it, other dimensions and policies were not measured ahead.
+    static constexpr bool kLeanWords = D == 3 && KC <= 10;
     const double *mu;    // LDS [KC][D]
     const double *logc;  // LDS [KC]
     struct Coef {
@@ -625,12 +631,43 @@ __device__ __forceinline__ void lds_trade(int64_t &v, unsigned long long *slot)
 {
     v = (int64_t)__hip_atomic_exchange(slot, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+// Which builds of the lane kernels (fast_kernel, screened_kernel) shed the integer bookkeeping around trades and draws -- a
+// policy's kLeanWords, never the batch builds:
+//   the parked words of two 32-bit fields trade their halves one by one (lds_trade<true>),
+//   the Philox counter words are formed once per launch where the launch allows it (PhiloxDraws::init_step),
+//   a kept row is addressed by one widening multiply-add (kept_row).
+// Same chains bit for bit.  A trait and not the rule: dense Bingham at d = 8, 9 grows by 6 - 38 registers with the half-word
+// trades and loses a wavefront per SIMD, and the eigenbasis Bingham build of d = 10 was 0.6 % behind with all three.
+template <class TP, class = void>
+struct lean_words : std::false_type {};
+template <class TP>
+struct lean_words<TP, std::enable_if_t<TP::kLeanWords>> : std::true_type {};
+
+// A word of two 32-bit fields (low half, high half).  HALVES: the halves trade one by one, at slot and slot + 4 bytes -- glued
+// into one 64-bit value, each field is moved into an aligned register pair before the exchange and out of it afterwards (the
+// halves live in unrelated registers).  Same bytes in the same places either way, and as the 64-bit stores that fill the slot.
+typedef uint32_t __attribute__((may_alias)) lds_half_t;
+template <bool HALVES>
+__device__ __forceinline__ void lds_trade_words(uint32_t &a, uint32_t &b, unsigned long long *slot)
+{
+    if constexpr (HALVES) {
+        lds_half_t *h = reinterpret_cast<lds_half_t *>(slot);
+        a = __hip_atomic_exchange(h, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        b = __hip_atomic_exchange(h + 1, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else {
+        const unsigned long long mine = (unsigned long long)a | ((unsigned long long)b << 32);
+        const unsigned long long o = __hip_atomic_exchange(slot, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        a = (uint32_t)o;
+        b = (uint32_t)(o >> 32);
+    }
+}
+template <bool HALVES>
 __device__ __forceinline__ void lds_trade(int32_t &a, int32_t &b, unsigned long long *slot)
 {
-    const unsigned long long mine = (unsigned long long)(uint32_t)a | ((unsigned long long)(uint32_t)b << 32);
-    const unsigned long long o = __hip_atomic_exchange(slot, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    a = (int32_t)(uint32_t)o;
-    b = (int32_t)(uint32_t)(o >> 32);
+    uint32_t ua = (uint32_t)a, ub = (uint32_t)b;
+    lds_trade_words<HALVES>(ua, ub, slot);
+    a = (int32_t)ua;
+    b = (int32_t)ub;
 }
 
 // The threshold a step's tries are held against (accept iff level(theta) > threshold) is formed from the level of x that make()
@@ -796,12 +833,17 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
     int32_t slot = 0;               // which of the lane's two chains `cur` is
     int32_t parked_status = kDone;  // status of the chain in LDS
 
+    constexpr bool kLean = !BATCH && lean_words<TP>::value;  // (lean_words: the bookkeeping this build sheds)
     auto chain_id = [&]() { return slot ? id1 : id0; };
     auto philox = [&]() {
         PhiloxDraws<V, true> dr;
         dr.tab = tab;
-        dr.init(a, chain_id(), D);
-        dr.begin_step(a.step_offset + (uint64_t)cur.steps_done);
+        if constexpr (kLean) {
+            dr.init_step(a, chain_id(), cur.steps_done, D);
+        } else {
+            dr.init(a, chain_id(), D);
+            dr.begin_step(a.step_offset + (uint64_t)cur.steps_done);
+        }
         return dr;
     };
     auto replay_take = [&]() -> double {
@@ -943,8 +985,14 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
             ++cur.steps_done;
             if ((a.samples != nullptr || STATS) && cur.steps_done == (cur.row + 1) * thin) {
                 if (a.samples != nullptr) {
+                    if constexpr (kLean) {
+                        const KeptRow kr = kept_row(a, cur.row, D, chain_id());
 #pragma unroll
-                    for (int j = 0; j < D; ++j) a.samples[sample_index(a, cur.row, j, D, chain_id())] = cur.x[j];
+                        for (int j = 0; j < D; ++j) kr.p[(int64_t)j * kr.step] = cur.x[j];
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < D; ++j) a.samples[sample_index(a, cur.row, j, D, chain_id())] = cur.x[j];
+                    }
                 }
                 if constexpr (STATS) stats_update<D>(a, chain_id(), cur.x);
                 ++cur.row;
@@ -972,17 +1020,17 @@ __global__ void __launch_bounds__(kBlock) fast_kernel(TargetBlock tb, RunBlock a
         word(cur.hi);
         word(cur.thr);
         word(cur.lvl);
-        lds_trade(cur.steps_done, cur.row, p);
+        lds_trade<kLean>(cur.steps_done, cur.row, p);
         p += kBlock;
         if (REPLAY) {
             int32_t zero = 0;
-            lds_trade(cur.cursor, zero, p);
+            lds_trade<kLean>(cur.cursor, zero, p);
             p += kBlock;
         }
         // (n_try, t | status << 26 | err << 28); the status also stays in a register for the wave-level votes
         const int32_t st = cur.status;
         int32_t nt = (int32_t)cur.n_try, packed = cur.t | (cur.status << 26) | (int32_t)((uint32_t)cur.err << 28);
-        lds_trade(nt, packed, p);
+        lds_trade<kLean>(nt, packed, p);
         cur.n_try = (uint32_t)nt;
         cur.t = packed & 0x3FFFFFF;
         cur.status = (packed >> 26) & 3;

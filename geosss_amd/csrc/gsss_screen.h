@@ -837,12 +837,13 @@ __device__ __forceinline__ void svc_count_flush(const unsigned long long (&c)[8]
 }
 #endif
 
+template <bool HALVES>  // (the halves one by one: lds_trade_words, gsss_fast.h)
 __device__ __forceinline__ void lds_trade(float &a, int32_t &b, unsigned long long *slot)
 {
-    const unsigned long long mine = (unsigned long long)__float_as_uint(a) | ((unsigned long long)(uint32_t)b << 32);
-    const unsigned long long o = __hip_atomic_exchange(slot, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    a = __uint_as_float((uint32_t)o);
-    b = (int32_t)(uint32_t)(o >> 32);
+    uint32_t ua = __float_as_uint(a), ub = (uint32_t)b;
+    lds_trade_words<HALVES>(ua, ub, slot);
+    a = __uint_as_float(ua);
+    b = (int32_t)ub;
 }
 
 // n / d and whether d divides n, exactly, for 0 <= n < 2^31 and a wavefront-uniform 0 < d < 2^31 (rcp = 1.0 / d): the
@@ -863,12 +864,13 @@ __device__ __forceinline__ bool divides(int32_t n, int32_t d, double rcp, int32_
     return r == 0;
 }
 
+template <bool HALVES>
 __device__ __forceinline__ void lds_trade(float &a, float &b, unsigned long long *slot)
 {
-    const unsigned long long mine = (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b) << 32);
-    const unsigned long long o = __hip_atomic_exchange(slot, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    a = __uint_as_float((uint32_t)o);
-    b = __uint_as_float((uint32_t)(o >> 32));
+    uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
+    lds_trade_words<HALVES>(ua, ub, slot);
+    a = __uint_as_float(ua);
+    b = __uint_as_float(ub);
 }
 
 // wavefronts per SIMD a plain launch is built for; the shared batch build (BatchShared) of the three batch targets: their own figure
@@ -968,12 +970,17 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
     StatsLane<D> sl;
     const bool stats_onchip = STATS && a.stats_onchip > 0;
 
+    constexpr bool kLean = !BATCH && lean_words<TP>::value;  // (lean_words, gsss_fast.h: the bookkeeping this build sheds)
     auto chain_id = [&]() { return slot ? id1 : id0; };
     auto philox = [&]() {
         PhiloxDraws<V, true> dr;
         dr.tab = tab;
-        dr.init(a, chain_id(), D);
-        dr.begin_step(a.step_offset + (uint64_t)cur.steps_done);
+        if constexpr (kLean) {
+            dr.init_step(a, chain_id(), cur.steps_done, D);
+        } else {
+            dr.init(a, chain_id(), D);
+            dr.begin_step(a.step_offset + (uint64_t)cur.steps_done);
+        }
         return dr;
     };
     auto replay_take = [&]() -> double {
@@ -1216,6 +1223,10 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
 #pragma unroll
                             for (int j = 0; j < D; ++j) p[j] = cur.x[j];
                         }
+                    } else if constexpr (kLean) {
+                        const KeptRow kr = kept_row(a, cur.row, D, chain_id());
+#pragma unroll
+                        for (int j = 0; j < D; ++j) kr.p[(int64_t)j * kr.step] = cur.x[j];
                     } else {
 #pragma unroll
                         for (int j = 0; j < D; ++j) a.samples[sample_index(a, cur.row, j, D, chain_id())] = cur.x[j];
@@ -1253,28 +1264,28 @@ __global__ void __launch_bounds__(kBlock, (STATS || (REPLAY && !NUMPY)) ? 1 : (N
         word(cur.hi);
         if constexpr (Chain::kCompact) {
             if (REPLAY) word(cur.thr);
-            lds_trade(cur.q[0], cur.q[1], p);
+            lds_trade<kLean>(cur.q[0], cur.q[1], p);
             p += kBlock;
-            lds_trade(cur.q[2], cur.steps_done, p);
+            lds_trade<kLean>(cur.q[2], cur.steps_done, p);
             p += kBlock;
         } else {
             if (!Chain::kRegenThr || REPLAY) word(cur.thr);
 #pragma unroll
             for (int i = Chain::kSkip; i < Chain::kQ; i += 2) {
-                lds_trade(cur.q[i], cur.q[i + 1], p);
+                lds_trade<kLean>(cur.q[i], cur.q[i + 1], p);
                 p += kBlock;
             }
-            lds_trade(cur.steps_done, cur.row, p);
+            lds_trade<kLean>(cur.steps_done, cur.row, p);
             p += kBlock;
         }
         if (REPLAY) {
             int32_t zero = 0;
-            lds_trade(cur.cursor, zero, p);
+            lds_trade<kLean>(cur.cursor, zero, p);
             p += kBlock;
         }
         const int32_t st = cur.status;
         int32_t nt = (int32_t)cur.n_try, packed = pack_flags();
-        lds_trade(nt, packed, p);
+        lds_trade<kLean>(nt, packed, p);
         cur.n_try = (uint32_t)nt;
         cur.t = packed & 0x1FFFFFF;
         cur.status = (packed >> 25) & 7;
