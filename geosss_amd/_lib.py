@@ -15,6 +15,7 @@ CHAIN_MAX_TRIES, CHAIN_NONFINITE, CHAIN_REPLAY_EXHAUSTED, CHAIN_COUNTER_SATURATE
 ABI_VERSION = 10
 STATS_NO_SECOND_MOMENT = 1
 MOMENTS_DIAG = 1
+MIXING_TRANSITIONS = 1
 
 
 class GsssError(RuntimeError):
@@ -72,6 +73,9 @@ SIGNATURES = {
     "gsss_autocov_rows": (C.c_int64, [C.c_int32, C.c_int32]),
     "gsss_target_autocov": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
                                       C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
+    "gsss_mixing_rows": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gsss_target_mixing": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gsss_last_launch": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gsss_batch_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

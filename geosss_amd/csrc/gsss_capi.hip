@@ -15,6 +15,7 @@
 #include "gsss_launch.h"
 #include "gsss_mh.h"
 #include "gsss_autocov.h"
+#include "gsss_mixing.h"
 #include "gsss_moments.h"
 #include "gsss_user_target.h"
 
@@ -1510,6 +1511,53 @@ int gsss_target_autocov(const double *ring_dev, int64_t ring_rows, int64_t first
     if (!guard.ok) return GSSS_E_HIP;
     return launch_target_autocov(ring_dev, ring_rows, first_row, n_rows, n_hist, n_chains, d, chains_per_target, n_lags, acc_dev,
                                  static_cast<hipStream_t>(stream));
+}
+
+int64_t gsss_mixing_rows(int32_t n_modes, int32_t flags)
+{
+    if (n_modes < 0 || (flags & ~GSSS_MIXING_TRANSITIONS)) return GSSS_E_INVALID;
+    if (n_modes > kMixingMaxModes) return GSSS_E_UNSUPPORTED;
+    return mixing_counters(n_modes, (flags & GSSS_MIXING_TRANSITIONS) != 0);
+}
+
+int gsss_target_mixing(const double *ring_dev, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist, int64_t n_chains,
+                       int32_t d, int64_t chains_per_target, const double *dirs_dev, int32_t n_modes, int32_t flags, double *step_dev,
+                       int64_t *count_dev, int device, void *stream)
+{
+    if (d < 2 || n_modes < 0 || (flags & ~GSSS_MIXING_TRANSITIONS)) {
+        set_error("gsss_target_mixing: need d >= 2, n_modes >= 0 and known flags (d = %d, n_modes = %d, flags = %d)", d, n_modes,
+                  flags);
+        return GSSS_E_INVALID;
+    }
+    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
+        set_error("gsss_target_mixing: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
+                  (long long)chains_per_target);
+        return GSSS_E_INVALID;
+    }
+    if (ring_rows < 0 || first_row < 0 || n_rows < 0 || n_hist < 0 || n_rows > ring_rows || first_row > ring_rows - n_rows) {
+        set_error("gsss_target_mixing: the rows %lld .. + %lld do not lie in a ring of %lld rows", (long long)first_row,
+                  (long long)n_rows, (long long)ring_rows);
+        return GSSS_E_INVALID;
+    }
+    if (n_hist > 1 || n_hist > ring_rows - n_rows) {
+        set_error("gsss_target_mixing: n_hist (%lld) exceeds the one row of history or the ring's rows outside the block (%lld)",
+                  (long long)n_hist, (long long)(ring_rows - n_rows));
+        return GSSS_E_INVALID;
+    }
+    if (n_modes > kMixingMaxModes) {
+        set_error("gsss_target_mixing: at most %d mode directions are kept (n_modes = %d)", kMixingMaxModes, n_modes);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    if (!ring_dev || !dirs_dev || !step_dev || !count_dev) {
+        set_error("gsss_target_mixing: %s is null",
+                  !ring_dev ? "ring_dev" : (!dirs_dev ? "dirs_dev" : (!step_dev ? "step_dev" : "count_dev")));
+        return GSSS_E_INVALID;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    return launch_target_mixing(ring_dev, ring_rows, first_row, n_rows, n_hist, n_chains, d, chains_per_target, dirs_dev, n_modes,
+                                (flags & GSSS_MIXING_TRANSITIONS) != 0, step_dev, count_dev, static_cast<hipStream_t>(stream));
 }
 
 int gsss_mode_supported(const gsss_target *t, int32_t mode)

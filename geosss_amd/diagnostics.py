@@ -16,7 +16,8 @@ import torch
 
 __all__ = ["acf", "acf_fft", "IAT", "n_eff", "distance", "hopping_frequency", "mode_occupancy", "mode_kl", "from_running",
            "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments",
-           "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw", "target_autocov", "from_target_autocov"]
+           "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw", "target_autocov", "from_target_autocov",
+           "target_mixing", "from_target_mixing"]
 
 
 def _t(x):
@@ -553,6 +554,133 @@ def from_target_autocov(acov, chains_per_target, n):
     return {"acf": ac, "iat": iat, "ess_within": m * n.reshape(-1, 1) / iat, "iat_truncated": ~pair_sum_went_negative(ac)}
 
 
+def _mixing_dirs(hop, modes, M, d, device):
+    """(dirs (M, 1 + K, d) contiguous float64 on `device`, K) from hop (d,) | (M, d) | None and modes (K, d) | (M, K, d) | None;
+    the shared forms are broadcast, hop=None is a zero direction (no hops), modes=None K = 0."""
+    def tensor(v, what):
+        try:
+            return _t(v).to(torch.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what} must be an array of directions") from e
+    h = torch.zeros((M, d), dtype=torch.float64) if hop is None else tensor(hop, "hop")
+    if h.ndim == 1:
+        h = h[None].expand(M, -1)
+    if h.ndim != 2 or tuple(h.shape) != (M, d):
+        raise ValueError(f"hop must be ({d},) or ({M}, {d}) (got {tuple(_t(hop).shape)})")
+    k = torch.zeros((M, 0, d), dtype=torch.float64) if modes is None else tensor(modes, "modes")
+    if k.ndim == 2:
+        k = k[None].expand(M, -1, -1)
+    if k.ndim != 3 or k.shape[0] != M or k.shape[2] != d:
+        raise ValueError(f"modes must be (K, {d}) or ({M}, K, {d}) (got {tuple(_t(modes).shape)})")
+    K = int(k.shape[1])
+    if K > 16:
+        raise ValueError(f"at most 16 mode directions are kept (got {K})")
+    return torch.cat([h[:, None, :].to(device), k.to(device)], dim=1).contiguous(), K
+
+
+def target_mixing(x, chains_per_target, *, hop=None, modes=None, transitions=False, step=None, counts=None, hist=None):
+    """Per-target mixing sums of a block of draws on the device, in one pass (gsss_target_mixing, include/gsss.h), every target
+    with its own directions.
+
+    x: a CUDA float64 tensor, component-major (R, d, n) -- what `advance(..., thin=t)` returns.  Target t owns the chains
+    [t m, (t + 1) m), m = chains_per_target, M = n / m.  hop: (d,) or (M, d), the direction whose equator a hop crosses (None:
+    a zero direction, no hops); modes: (K, d) or (M, K, d), K <= 16 (None: K = 0).  Returns (step, counts): step (M, 2) =
+    sum theta, sum theta^2 over the target's pairs of consecutive draws, theta = arccos(clip(x_r . x_{r-1}, -1, 1)); counts
+    (M, 3 + K [+ K K]) int64 = draws, pairs, hops, the draws per mode (first maximum of x . mode_k, like np.argmax) and, with
+    transitions=True, the pairs by [mode before][mode after].  `hist`: the one row (1, d, n) that precedes x, for a caller who
+    streams a series block by block; `step` / `counts` continue earlier accumulators (added to, returned).
+    -> `from_target_mixing`."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.ndim != 3:
+        raise ValueError("x must be a CUDA float64 tensor (R, d, n)")
+    R, d, n = (int(v) for v in x.shape)
+    m = int(chains_per_target)
+    if m < 1 or n % m:
+        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+    if d < 2:
+        raise ValueError("a point on a sphere has two coordinates at least")
+    M, h = n // m, 0
+    dirs, K = _mixing_dirs(hop, modes, M, d, x.device)
+    if not x.is_cuda:
+        raise ValueError("x must be a CUDA float64 tensor (R, d, n): the sums are taken on the device")
+    rows = 3 + K + (K * K if transitions else 0)
+    if hist is not None:
+        if (not isinstance(hist, torch.Tensor) or hist.ndim != 3 or tuple(hist.shape[1:]) != (d, n) or hist.dtype != torch.float64
+                or hist.device != x.device or hist.shape[0] > 1):
+            raise ValueError("hist must be a float64 tensor of at most one row shaped like the rows of x, on the device of x")
+        h = int(hist.shape[0])
+    if step is None:
+        step = torch.zeros((M, 2), dtype=torch.float64, device=x.device)
+    elif (not isinstance(step, torch.Tensor) or tuple(step.shape) != (M, 2) or step.dtype != torch.float64 or step.device != x.device
+          or not step.is_contiguous()):
+        raise ValueError(f"step must be a contiguous float64 tensor ({M}, 2) on the device of x")
+    if counts is None:
+        counts = torch.zeros((M, rows), dtype=torch.int64, device=x.device)
+    elif (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (M, rows) or counts.dtype != torch.int64
+          or counts.device != x.device or not counts.is_contiguous()):
+        raise ValueError(f"counts must be a contiguous int64 tensor ({M}, {rows}) on the device of x")
+    if R == 0 or n == 0:
+        return step, counts
+    ring = torch.cat([x, hist]) if h else x.contiguous()     # the row before row 0 of a ring is its last
+    _mixing_fold(ring, 0, R, h, m, dirs, K, transitions, step, counts)
+    return step, counts
+
+
+def _mixing_fold(ring, first_row, n_rows, n_hist, m, dirs, n_modes, transitions, step, counts):
+    """gsss_target_mixing on the rows first_row .. + n_rows of a contiguous ring (rows, d, n)."""
+    from . import _lib
+    from .sphere import current_stream_ptr
+    rows, d, n = (int(v) for v in ring.shape)
+    dev = ring.device.index if ring.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsss_target_mixing(ring.data_ptr(), rows, first_row, n_rows, n_hist, n, d, m, dirs.data_ptr(), n_modes,
+                                                  _lib.MIXING_TRANSITIONS if transitions else 0, step.data_ptr(), counts.data_ptr(),
+                                                  dev, current_stream_ptr(dev)))
+
+
+def from_target_mixing(step, counts, n_modes, *, weights=None):
+    """Per-target mixing metrics from the accumulators of `target_mixing` / `Sampler.summarize(mixing=)`: step (M, 2), counts
+    (M, 3 + K [+ K K]), K = n_modes.  With N draws and P pairs per target:
+
+        geodesic_step = sum theta / P,  geodesic_step_sd = sqrt(max(sum theta^2 / P - geodesic_step^2, 0)),
+        hop_frequency = hops / P,  mode_occupancy (M, K) = mode counts / N,
+
+    and, where the transitions were counted, mode_transitions (M, K, K), every row [mode before] divided by its sum (NaN for a
+    mode no pair left), and mode_switch_frequency = the share of the pairs whose two draws have different modes.  weights (K,)
+    or (M, K): mode_kl (M,) = KL(mode_occupancy || weights) with `mode_kl`'s 1e-100 floor; weights without modes are refused.
+    CPU or CUDA tensors."""
+    step = _t(step).to(torch.float64)
+    counts = _t(counts)
+    K = int(n_modes)
+    if step.ndim != 2 or step.shape[1] != 2 or counts.ndim != 2 or counts.shape[0] != step.shape[0]:
+        raise ValueError("step must be (M, 2) and counts (M, 3 + K [+ K K])")
+    if K < 0 or counts.shape[1] not in (3 + K, 3 + K + K * K):
+        raise ValueError(f"counts must have 3 + K or 3 + K + K K columns for K = {K} (got {counts.shape[1]})")
+    M = int(step.shape[0])
+    c = counts.to(torch.float64)
+    n, pairs = c[:, 0], c[:, 1]
+    mean = step[:, 0] / pairs
+    out = {"geodesic_step": mean,
+           "geodesic_step_sd": torch.sqrt(torch.clamp(step[:, 1] / pairs - mean * mean, min=0.0)),
+           "hop_frequency": c[:, 2] / pairs,
+           "mode_occupancy": c[:, 3:3 + K] / n[:, None]}
+    if K > 0 and counts.shape[1] == 3 + K + K * K:
+        tr = c[:, 3 + K:].reshape(M, K, K)
+        out["mode_transitions"] = tr / tr.sum(-1, keepdim=True)
+        out["mode_switch_frequency"] = (pairs - torch.diagonal(tr, dim1=1, dim2=2).sum(-1)) / pairs
+    if weights is not None:
+        if K == 0:
+            raise ValueError("mode_kl compares the mode occupancy with the weights: there are no modes")
+        w = _t(weights).to(c)
+        if w.ndim == 1:
+            w = w[None].expand(M, -1)
+        if tuple(w.shape) != (M, K):
+            raise ValueError(f"weights must be ({K},) or ({M}, {K})")
+        p = out["mode_occupancy"]
+        p = torch.where(p > 0, p, torch.full_like(p, 1e-100))
+        out["mode_kl"] = (p * torch.log(p / w)).sum(-1)
+    return out
+
+
 class TargetMoments:
     """What `Sampler.summarize` returns: the per-target accumulators of a run (`acc` (M, rows), `chain_sum` (d, n), device
     tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`.
@@ -566,7 +694,14 @@ class TargetMoments:
     With `summarize(log_prob=True)` also the log-density trace: `lp_acc` (M, 3) -- count, sum, sum of squares of log_prob over
     the target's draws --, `lp_chain_sum` (n,), and the best draw seen per target, `lp_best` (M,) and `x_best` (M, d): the maximum
     of log_prob over all retained draws (ties: the earliest draw, then the lowest chain).  stats() then adds lp_mean, lp_var,
-    lp_rhat, lp_ess_between (`from_scalar_moments`), lp_best and x_best."""
+    lp_rhat, lp_ess_between (`from_scalar_moments`), lp_best and x_best.
+
+    With `summarize(mixing=)` also the step, hop and mode counts of every target against its own directions: `mix_step` (M, 2)
+    and `mix_counts` (M, 3 + K [+ K K]) (see `target_mixing`), `mix_modes` = K, `mix_weights` (M, K) or None, the directions
+    `mix_dirs` (M, 1 + K, d) and whether the transitions are counted, from which into= goes on; without lags `hist` is the one
+    last retained row, so that the pair at the seam of two calls counts exactly once.  stats() then adds geodesic_step,
+    geodesic_step_sd, hop_frequency, mode_occupancy and, where they apply, mode_transitions, mode_switch_frequency and mode_kl
+    (`from_target_mixing`)."""
 
     def __init__(self, acc, chain_sum, d, chains_per_target, second_moment, lp_acc=None, lp_chain_sum=None, lp_best=None,
                  x_best=None):
@@ -574,6 +709,8 @@ class TargetMoments:
         self.chains_per_target, self.second_moment = int(chains_per_target), bool(second_moment)
         self.lp_acc, self.lp_chain_sum, self.lp_best, self.x_best = lp_acc, lp_chain_sum, lp_best, x_best
         self.lags, self.acov, self.hist, self.lp_acov, self.lp_hist = None, None, None, None, None
+        self.mix_step, self.mix_counts, self.mix_modes, self.mix_weights = None, None, None, None
+        self.mix_dirs, self.mix_transitions = None, False
 
     @property
     def n_targets(self):
@@ -601,6 +738,8 @@ class TargetMoments:
             if self.lp_acov is not None:
                 lp = from_target_autocov(self.lp_acov, self.chains_per_target, per_chain)
                 out.update({"lp_" + key: val[:, 0] for key, val in lp.items()})
+        if self.mix_step is not None:
+            out.update(from_target_mixing(self.mix_step, self.mix_counts, self.mix_modes, weights=self.mix_weights))
         return out
 
 

@@ -583,6 +583,19 @@ class TargetBatch(Distribution):
                                                C.byref(grid), C.byref(use)))
         return {"chains_per_workgroup": cpw.value, "targets_per_workgroup": tpw.value, "grid": grid.value, "lane_use": use.value}
 
+    def mixing_directions(self):
+        """The directions `summarize(mixing=True)` holds every member's draws against -- what `enable_stats` would choose for
+        the member alone: -> (hop (M, d), modes (M, K, d), weights (M, K) or None), numpy arrays.  vMF and vMF-mixture members:
+        modes = the terms' mu (`MixtureModel._modes()`), weights = the member's, hop = its first mode.  Bingham and
+        BinghamFisher members: hop = `.mode`, no modes (K = 0) and no weights."""
+        if not isinstance(self.pdfs[0], Bingham):      # (the members are of one family)
+            modes = np.array([[p.mu] if isinstance(p, VonMisesFisher) else p._modes() for p in self.pdfs], dtype=np.float64)
+            weights = np.array([[1.0] if isinstance(p, VonMisesFisher) else [w for _, w in p._terms()] for p in self.pdfs],
+                               dtype=np.float64)
+            return modes[:, 0, :].copy(), modes, weights
+        hop = np.array([p.mode for p in self.pdfs], dtype=np.float64)
+        return hop, np.zeros((len(self.pdfs), 0, self.d)), None
+
     def _batch_handle(self, device=None):
         """A device copy of the batch for evaluation: any cached one of the device whose parameters are current (the members'
         blobs do not depend on the chains per target), else a new one with one chain per target."""

@@ -619,7 +619,7 @@ class RejectionSphericalSliceSampler:
         return out[0] if self._single else out
 
     def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None,
-                  log_prob=False, lags=None):
+                  log_prob=False, lags=None, mixing=False):
         """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
         would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
         windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
@@ -651,7 +651,19 @@ class RejectionSphericalSliceSampler:
         and the log-density series is folded the same way: lp_acf, lp_iat, lp_ess_within, lp_iat_truncated.  n_samples <= L is
         refused; a summary begun without lags cannot take them up.  The chains, the final state and -- window for window -- the
         moments are those of the default; where the ring's end cuts a window that the default would not cut, acc and chain_sum
-        may differ from the default's in the last bits (per-window partial sums are added)."""
+        may differ from the default's in the last bits (per-window partial sums are added).
+
+        mixing=True (a TargetBatch sampler) or mixing=dict(hop=, modes=, weights=, transitions=) (any sampler): also what the
+        paper judges a sampler by, per target and against the target's OWN directions -- the mean geodesic step between
+        consecutive retained draws, the hopping frequency across the equator of `hop` and the occupancy of `modes`, with its KL
+        divergence against `weights` -- which tell apart what R-hat cannot: chains that all sit in one mode.  True takes
+        `TargetBatch.mixing_directions()` of the targets this sampler samples; the dict's hop is (d,) or (M, d), its modes (K, d)
+        or (M, K, d), its weights (K,) or (M, K), for the M targets of this sampler.  The buffer becomes a ring with at least
+        one row of history (max(lags, 1) + window rows) and every window is folded by gsss_target_mixing beside the other
+        folds.  The result carries `mix_step`, `mix_counts`, `mix_modes`, `mix_weights`; stats() adds geodesic_step,
+        geodesic_step_sd, hop_frequency, mode_occupancy, mode_kl (with weights) and, with transitions=True, mode_transitions
+        and mode_switch_frequency (diagnostics.from_target_mixing).  into= continues them with the directions they were begun
+        with, the pair at the seam counted once; a summary begun without mixing cannot take it up."""
         from . import diagnostics
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")
@@ -677,6 +689,21 @@ class RejectionSphericalSliceSampler:
             if into is None and int(n_samples) <= int(lags):
                 raise ValueError(f"the autocorrelation needs more than `lags` retained draws per chain (n_samples = {n_samples}, "
                                  f"lags = {lags})")
+        mix = None
+        if mixing is not None and mixing is not False:
+            if mixing is True:
+                if self._batch_m is None:
+                    raise ValueError("summarize(mixing=True) takes the directions of a TargetBatch's members: pass "
+                                     "mixing=dict(hop=, modes=, weights=) for a single target")
+                t0 = self.chain_offset // m
+                hop, modes, weights = self.target.mixing_directions()
+                mix = {"hop": hop[t0:t0 + n // m], "modes": modes[t0:t0 + n // m],
+                       "weights": None if weights is None else weights[t0:t0 + n // m], "transitions": False}
+            elif isinstance(mixing, dict) and not set(mixing) - {"hop", "modes", "weights", "transitions"}:
+                mix = {"hop": mixing.get("hop"), "modes": mixing.get("modes"), "weights": mixing.get("weights"),
+                       "transitions": bool(mixing.get("transitions", False))}
+            else:
+                raise ValueError("mixing must be True or a dict with the keys hop, modes, weights, transitions")
         full, rows = diagnostics._moments_form(d, second_moment if into is None or second_moment is not None else into.second_moment)
         if into is None:
             into = diagnostics.TargetMoments(torch.zeros((n // m, rows), dtype=torch.float64, device=self._tdev),
@@ -691,6 +718,18 @@ class RejectionSphericalSliceSampler:
                 into.acov = torch.zeros((n // m, d, into.lags + 1, 3), dtype=torch.float64, device=self._tdev)
                 if log_prob:
                     into.lp_acov = torch.zeros((n // m, 1, into.lags + 1, 3), dtype=torch.float64, device=self._tdev)
+            if mix is not None:
+                into.mix_dirs, into.mix_modes = diagnostics._mixing_dirs(mix["hop"], mix["modes"], n // m, d, self._tdev)
+                into.mix_transitions = mix["transitions"]
+                if mix["weights"] is not None:
+                    w = diagnostics._t(mix["weights"]).to(torch.float64)
+                    w = w[None].expand(n // m, -1) if w.ndim == 1 else w
+                    if into.mix_modes == 0 or tuple(w.shape) != (n // m, into.mix_modes):
+                        raise ValueError(f"weights must be (K,) or (M, K) = ({n // m}, {into.mix_modes}), one per mode direction")
+                    into.mix_weights = w.contiguous().to(self._tdev)
+                cols = 3 + into.mix_modes + (into.mix_modes ** 2 if into.mix_transitions else 0)
+                into.mix_step = torch.zeros((n // m, 2), dtype=torch.float64, device=self._tdev)
+                into.mix_counts = torch.zeros((n // m, cols), dtype=torch.int64, device=self._tdev)
         elif (into.d != d or into.chains_per_target != m or into.second_moment != full or tuple(into.acc.shape) != (n // m, rows)
               or tuple(into.chain_sum.shape) != (d, n)):
             raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
@@ -699,11 +738,16 @@ class RejectionSphericalSliceSampler:
         elif lags is not None and into.lags != int(lags):
             raise ValueError("into= was begun without these lags: the lagged products of its draws so far were not kept, so it "
                              "cannot take them up")
+        elif mix is not None and into.mix_step is None:
+            raise ValueError("into= was begun without mixing: the steps and counts of its draws so far were not kept, so it "
+                             "cannot take them up")
         log_prob = into.lp_acc is not None
+        mixing = into.mix_step is not None
         L = into.lags or 0
+        H = max(L, 1) if mixing else L                # rows of history the ring keeps
         rest = int(n_samples) - 1
         if window is None:                            # (with lags the ring of L + window rows is what stays under 256 MiB)
-            window = max(1, (256 << 20) // (8 * d * n) - L)
+            window = max(1, (256 << 20) // (8 * d * n) - H)
         window = int(window)
         if window < 1:
             raise ValueError("window must be >= 1")
@@ -712,9 +756,9 @@ class RejectionSphericalSliceSampler:
         if burnin:
             self.advance(burnin)
 
-        rows = L + window
+        rows = H + window
         lp_buf = torch.empty((rows, n), dtype=torch.float64, device=self._tdev) if log_prob else None
-        buf = torch.empty((rows, d, n), dtype=torch.float64, device=self._tdev) if rest or L else None
+        buf = torch.empty((rows, d, n), dtype=torch.float64, device=self._tdev) if rest or H else None
 
         def fold(x, first=0, hist=0):
             """x: a window (w, d, n); with lags it is the rows first .. of the ring, behind `hist` rows of history"""
@@ -729,11 +773,14 @@ class RejectionSphericalSliceSampler:
                 diagnostics.scalar_moments(lp, m, acc=into.lp_acc, chain_sum=into.lp_chain_sum)
                 into.update_best(lp, x)
             if L:
-                diagnostics._autocov_fold(buf, first, w, hist, m, L, into.acov)
+                diagnostics._autocov_fold(buf, first, w, min(L, hist), m, L, into.acov)
                 if log_prob:
-                    diagnostics._autocov_fold(lp_buf[:, None, :], first, w, hist, m, L, into.lp_acov)
+                    diagnostics._autocov_fold(lp_buf[:, None, :], first, w, min(L, hist), m, L, into.lp_acov)
+            if mixing:
+                diagnostics._mixing_fold(buf, first, w, min(1, hist), m, into.mix_dirs, into.mix_modes, into.mix_transitions,
+                                         into.mix_step, into.mix_counts)
 
-        if not L:
+        if not H:
             fold(self._state[None])                   # draw 0: the state itself is a (1, d, n) window
             done = 0
             while done < rest:
@@ -741,7 +788,7 @@ class RejectionSphericalSliceSampler:
                 fold(self.advance(w * thin, thin=thin, out=buf[:w]))
                 done += w
         else:
-            # The ring: the rows kept by an earlier call, draw 0, then window after window, none of which wraps; the L rows
+            # The ring: the rows kept by an earlier call, draw 0, then window after window, none of which wraps; the H rows
             # before a window (round the ring's end) are the L draws before it, where the kernel reads them.
             seen = 0 if into.hist is None else int(into.hist.shape[0])
             if seen:
@@ -754,9 +801,9 @@ class RejectionSphericalSliceSampler:
             while done < rest:
                 pos %= rows
                 w = min(window, rest - done, rows - pos)
-                fold(self.advance(w * thin, thin=thin, out=buf[pos:pos + w]), pos, min(L, seen))
+                fold(self.advance(w * thin, thin=thin, out=buf[pos:pos + w]), pos, min(H, seen))
                 pos, seen, done = pos + w, seen + w, done + w
-            last = (pos - min(L, seen) + torch.arange(min(L, seen), device=self._tdev)) % rows
+            last = (pos - min(H, seen) + torch.arange(min(H, seen), device=self._tdev)) % rows
             into.hist = buf[last]
             if log_prob:
                 into.lp_hist = lp_buf[last][:, None, :]

@@ -414,6 +414,35 @@ int gsss_target_autocov(const double *ring_dev, int64_t ring_rows, int64_t first
                         int64_t n_chains, int32_t d, int64_t chains_per_target, int32_t n_lags, double *acc_dev, int device,
                         void *stream);
 
+/* Per-TARGET mixing metrics of retained draws, streamed: the mean geodesic step between consecutive draws (sphere.py:64-68), the
+ * hopping frequency across a direction's equator (scripts/bingham.py:23-25) and the mode occupancy (scripts/vMF_diagnostics.py:
+ * 335-342), for ensembles in which target t owns the chains [t m, (t + 1) m), m = chains_per_target, and EVERY TARGET HAS ITS OWN
+ * DIRECTIONS -- the stats_dev step, hop and mode rows, which take one set of directions and which a batch refuses, by a kernel of
+ * its own beside the sampler, so it serves every kernel family, mode and dimension.  ring_dev is component-major
+ * [ring_rows][d][n_chains] with the block semantics of gsss_target_autocov: the block is the rows first_row .. first_row + n_rows
+ * - 1 (it does not wrap); with n_hist = 1 the draw that precedes it is the row (first_row - 1) mod ring_rows, read where it lies.
+ * A pair (r, r - 1) counts in the call whose block holds r.
+ * dirs_dev [n_chains / m][1 + n_modes][d], per target t: the hop direction h_t, then its K = n_modes mode directions (K = 0 .. 16).
+ * step_dev [n_chains / m][2], ADDED to: sum theta and sum theta^2 over the target's pairs, theta = acos(clamp(x_r . x_{r-1}, -1,
+ * 1)), the product a chain of fused multiply-adds in component order (the arithmetic of the stats_dev row).
+ * count_dev [n_chains / m][gsss_mixing_rows(n_modes, flags)], int64, ADDED to, per target:
+ *     0                draws
+ *     1                pairs
+ *     2                hops: pairs with sign(x_r . h_t) != sign(x_{r-1} . h_t), the three-valued sign of np.sign
+ *     3 .. 2 + K       draws whose mode is k: the FIRST maximum over k of x . mode_k, like np.argmax
+ *     .. + K K         with GSSS_MIXING_TRANSITIONS: pairs by [mode of x_{r-1}][mode of x_r]
+ * The two floating-point sums have an order fixed by the arguments and use no floating-point atomics: a call gives the same bits
+ * every time.  The counters are integers, added with integer atomics -- the same in any order.
+ * GSSS_E_INVALID: d < 2, m < 1, n_chains no multiple of m, a negative count, first_row + n_rows > ring_rows, n_hist > 1 or
+ * > ring_rows - n_rows, n_modes < 0, unknown flags, a NULL ring_dev / dirs_dev / step_dev / count_dev with a non-empty block;
+ * GSSS_E_UNSUPPORTED: n_modes > 16 (gsss_mixing_rows returns the same codes) -- all of them before the device is touched.
+ * n_rows = 0 does nothing.  The reference computes these from one stored chain on the host. */
+#define GSSS_MIXING_TRANSITIONS 1
+int64_t gsss_mixing_rows(int32_t n_modes, int32_t flags);
+int gsss_target_mixing(const double *ring_dev, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist,
+                       int64_t n_chains, int32_t d, int64_t chains_per_target, const double *dirs_dev, int32_t n_modes,
+                       int32_t flags, double *step_dev, int64_t *count_dev, int device, void *stream);
+
 /* 1 if gsss_run accepts `mode` for this target's shape (fast mode is built for the shapes listed in
  * geosss_amd/csrc/gsss_fast_*.hip), else 0. */
 int gsss_mode_supported(const gsss_target *t, int32_t mode);
