@@ -11,6 +11,7 @@
 
 #include "gsss_batch.h"
 #include "gsss_batch_logprob.h"
+#include "gsss_exchange.h"
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
@@ -1115,6 +1116,68 @@ int gsss_batch_logprob_draws(const gsss_target *t, const double *samples_dev, in
     tbb.blob += target0 * t->batch.stride;
     return launch_batch_logprob(vec, tbb, batch_points_draws(samples_dev, out_dev, n_rows, n_chains, m, tbb.d, t->batch.stride),
                                 n_chains / m, false, static_cast<hipStream_t>(stream));
+}
+
+int64_t gsss_exchange_scratch_doubles(int64_t n_chains) { return n_chains < 0 ? GSSS_E_INVALID : 2 * n_chains; }
+
+int gsss_batch_exchange(const gsss_target *t, double *state_dev, const int32_t *err_dev, int64_t n_chains, int64_t target0,
+                        int32_t ladder, int32_t parity, uint64_t seed, uint64_t chain_offset, uint64_t step, double *scratch_dev,
+                        int64_t *replica_dev, int64_t *counts_dev, double *log_alpha_out, void *stream)
+{
+    if (ladder < 2 || (parity != 0 && parity != 1)) {
+        set_error("gsss_batch_exchange: need ladder >= 2 and parity 0 or 1 (ladder = %d, parity = %d)", ladder, parity);
+        return GSSS_E_INVALID;
+    }
+    if (n_chains < 0 || target0 < 0 || target0 % ladder != 0) {
+        set_error("gsss_batch_exchange: n_chains (%lld) must be >= 0 and target0 (%lld) a multiple of the ladder (%d) >= 0",
+                  (long long)n_chains, (long long)target0, ladder);
+        return GSSS_E_INVALID;
+    }
+    if (!t) {
+        set_error("gsss_batch_exchange: null handle");
+        return GSSS_E_INVALID;
+    }
+    if (!is_batch(t)) {
+        set_error("gsss_batch_exchange takes a gsss_target_create_batch handle: a ladder is a run of a batch's members");
+        return GSSS_E_UNSUPPORTED;
+    }
+    const int64_t m = t->batch.m;
+    if (n_chains % (m * ladder) != 0 || target0 > t->batch.n_targets || n_chains / m > t->batch.n_targets - target0) {
+        set_error("gsss_batch_exchange: %lld chains from target %lld on are no run of whole ladders of %d members of the batch (%lld "
+                  "chains per target, %d targets)", (long long)n_chains, (long long)target0, ladder, (long long)m, t->batch.n_targets);
+        return GSSS_E_INVALID;
+    }
+    if (chain_offset + (uint64_t)n_chains > (1ull << 48) || step >= kInitStep) {
+        set_error("gsss_batch_exchange: chain ids and steps are 48-bit words of the stream's counter");
+        return GSSS_E_INVALID;
+    }
+    if (n_chains == 0) return GSSS_OK;
+    if (!state_dev || !err_dev || !scratch_dev) {
+        set_error("gsss_batch_exchange: %s is null", !state_dev ? "state_dev" : (!err_dev ? "err_dev" : "scratch_dev"));
+        return GSSS_E_INVALID;
+    }
+    const int vec = select_vec_for(t->tb, 0);
+    if (vec < 0) return vec;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return GSSS_E_HIP;
+    TargetBlock tbb = t->tb;
+    tbb.blob += target0 * t->batch.stride;
+    ExchangeBlock a{};
+    a.state = state_dev;
+    a.lp = scratch_dev;
+    a.err = err_dev;
+    a.replica = replica_dev;
+    a.counts = reinterpret_cast<unsigned long long *>(counts_dev);
+    a.log_alpha = log_alpha_out;
+    a.stride = t->batch.stride;
+    a.n = n_chains;
+    a.m = m;
+    a.R = ladder;
+    a.parity = parity;
+    a.seed = seed;
+    a.chain_offset = chain_offset;
+    a.step = step;
+    return launch_batch_exchange(vec, tbb, a, static_cast<hipStream_t>(stream));
 }
 
 int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)

@@ -514,6 +514,50 @@ class TargetBatch(Distribution):
                 raise ValueError("the Bingham members of a target batch all have a linear term b (BinghamFisher) or none has: "
                                  f"member 0 and member {i} differ")
 
+    @classmethod
+    def tempered(cls, pdf, betas):
+        """The ladder of one density for replica exchange (`sampler.exchange`, `advance(exchange=)`): member r is `pdf` at inverse
+        temperature betas[r], betas descending from 1 -- the coldest member, the density itself, first.  A list of densities
+        gives their ladders one behind the other (ladder-major: G R members, ladder g the members [g R, (g + 1) R)).
+
+          Bingham(A)            -> Bingham(beta A)              an exact power
+          BinghamFisher(A, b)   -> BinghamFisher(beta A, beta b) an exact power
+          VonMisesFisher(mu)    -> VonMisesFisher(beta mu)       an exact power (kappa = |mu| scales)
+          MixtureModel of vMF   -> the same weights, every term's mu scaled by beta
+
+        The last is a LADDER, NOT A POWER: p^beta of a mixture is no mixture, while the members of a batch must be of one family.
+        The exchange is exact all the same: a swap between members a and b is accepted with their own densities,
+        alpha = p_a(x_b) p_b(x_a) / (p_a(x_a) p_b(x_b)), which leaves the product law of the batch invariant whatever the
+        members are; the ladder only has to be flat enough at its hot end and close enough from rung to rung.  Any other class
+        raises a TypeError.  The result carries `ladder` = len(betas) and `betas`."""
+        pdfs = list(pdf) if isinstance(pdf, (list, tuple)) else [pdf]
+        betas = np.array(betas, dtype=np.float64)
+        if betas.ndim != 1 or len(betas) < 2 or betas[0] != 1.0 or np.any(np.diff(betas) >= 0) or betas[-1] < 0 or not np.all(np.isfinite(betas)):
+            raise ValueError("betas are at least two inverse temperatures, strictly descending from 1 and not below 0")
+        if not pdfs:
+            raise TypeError("a target batch needs at least one member")
+        members = []
+        for p in pdfs:
+            for beta in betas:
+                if type(p) is BinghamFisher:
+                    members.append(BinghamFisher(beta * p.A, beta * p.b))
+                elif type(p) is Bingham:
+                    members.append(Bingham(beta * p.A))
+                elif type(p) is VonMisesFisher:
+                    members.append(VonMisesFisher(beta * p.mu))
+                elif type(p) is MixtureModel and not p._marginal and all(type(q) is VonMisesFisher for q, _ in p._terms()):
+                    terms = p._terms()
+                    members.append(MixtureModel([VonMisesFisher(beta * q.mu) for q, _ in terms], [w for _, w in terms]))
+                elif type(p) is MixtureModel:
+                    raise TypeError("a MixtureModel with other than VonMisesFisher terms has no tempered ladder: ladders are built "
+                                    "of Bingham, BinghamFisher, VonMisesFisher and MixtureModel of vMF terms")
+                else:
+                    raise TypeError(f"{type(p).__name__} has no tempered ladder: ladders are built of Bingham, BinghamFisher, "
+                                    "VonMisesFisher and MixtureModel of vMF terms")
+        batch = cls(members)
+        batch.ladder, batch.betas = len(betas), betas
+        return batch
+
     @staticmethod
     def _family(kind):
         return {_lib.VMF_MIXTURE: "vMF mixture", _lib.BINGHAM: "Bingham target"}.get(kind, f"target of kind {kind}")

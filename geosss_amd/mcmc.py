@@ -264,6 +264,141 @@ class RejectionSphericalSliceSampler:
         if not fast_ok and not self.variant:
             _warn_exact_fallback(self.target)
 
+    # ------------------------------------------------------------------ replica exchange
+    _xchg = None             # scratch, replica ids and counts, allocated on the first use of exchange
+    _xchg_first = 0          # first chain of the sampler within those buffers (a chain block of sample())
+    _exchange_active = None  # the exchange= of the sample() / summarize() call in progress
+
+    def _exchange_plan(self, exchange):
+        """(R, k) of exchange=dict(ladder=R, every=k), and the refusals."""
+        if self._batch_m is None:
+            raise ValueError("replica exchange runs along ladders of a TargetBatch's members: this sampler holds no TargetBatch "
+                             "(TargetBatch.tempered builds the ladder of one density)")
+        if isinstance(exchange, tuple):
+            return exchange
+        if not isinstance(exchange, dict) or set(exchange) - {"ladder", "every"} or "ladder" not in exchange:
+            raise ValueError("exchange must be dict(ladder=R, every=k)")
+        R, k = int(exchange["ladder"]), int(exchange.get("every", 1))
+        M = self.n_chains // self._batch_m
+        if R < 2 or M % R or (self.chain_offset // self._batch_m) % R:
+            raise ValueError(f"the {M} targets of this sampler (from target {self.chain_offset // self._batch_m} on) are no run of "
+                             f"whole ladders of {R} members (ladder >= 2)")
+        if k < 1:
+            raise ValueError(f"every must be >= 1 (got {k})")
+        return R, k
+
+    @contextlib.contextmanager
+    def _exchanging(self, exchange):
+        keep = self._exchange_active
+        self._exchange_active = self._exchange_plan(exchange)
+        try:
+            self._exchange_buffers()
+            yield
+        finally:
+            self._exchange_active = keep
+
+    def _block_unit(self):
+        """Chains that stay together when sample() cuts the ensemble into blocks: a target's, a ladder's under exchange."""
+        return self._batch_m * (self._exchange_active[0] if self._exchange_active else 1)
+
+    def _exchange_buffers(self):
+        if self._xchg is None:
+            if self._xchg_first:
+                raise ValueError("the exchange buffers belong to the whole sampler: they cannot be created inside a chain block")
+            n = self.n_chains
+            self._xchg = {"scratch": torch.empty(int(self._lib.gsss_exchange_scratch_doubles(n)), dtype=torch.float64, device=self._tdev),
+                          "replica": torch.arange(n, dtype=torch.int64, device=self._tdev),
+                          "counts": torch.zeros((2, n // self._batch_m), dtype=torch.int64, device=self._tdev)}
+        return self._xchg
+
+    @property
+    def replica(self):
+        """int64 (n_chains,): which of the initial chains' trajectories slot c now holds (initially arange); the exchange moves
+        the entries with the state columns."""
+        return self._exchange_buffers()["replica"]
+
+    def exchange(self, ladder, parity=None, *, every=1, log_alpha=None):
+        """One replica-exchange sweep at the current step s (gsss_batch_exchange): the sampler's targets form ladders of
+        `ladder` consecutive members; member a = g R + 2 k + parity is paired with a + 1, chain i with chain i, and the two
+        states are swapped with probability min(1, alpha), log alpha = (l_a(x_b) - l_a(x_a)) + (l_b(x_a) - l_b(x_b)) with the
+        members' OWN log-densities -- exact for any ladder of members, powers of one density or not.  parity=None: the
+        schedule's, (s / every) % 2.  log_alpha: a float64 CUDA tensor (n_chains,) that receives log alpha at the lower chains.
+        Only states (and `replica`) move; n_tries, n_reject and errors stay per-target figures.  Chains with an error bit and
+        non-finite values are not exchanged."""
+        R, k = self._exchange_plan({"ladder": ladder, "every": every})
+        if parity is None:
+            parity = (self._step // k) % 2
+        if parity not in (0, 1):
+            raise ValueError("parity must be 0, 1 or None")
+        self._sweep(R, int(parity), log_alpha)
+
+    def _sweep(self, R, parity, log_alpha=None):
+        x, n, m, c0 = self._exchange_buffers(), self.n_chains, self._batch_m, self._xchg_first
+        whole = c0 == 0 and n == x["replica"].shape[0]
+        counts = x["counts"] if whole else torch.zeros((2, n // m), dtype=torch.int64, device=self._tdev)
+        if log_alpha is not None and (not isinstance(log_alpha, torch.Tensor) or tuple(log_alpha.shape) != (n,) or not log_alpha.is_cuda
+                                      or log_alpha.dtype != torch.float64 or not log_alpha.is_contiguous()):
+            raise ValueError("log_alpha must be a contiguous float64 CUDA tensor (n_chains,)")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.gsss_batch_exchange(
+                self._target_dev.handle, self._state.data_ptr(), self._err.data_ptr(), n, self.chain_offset // m, R, parity, self.seed,
+                self.chain_offset, self._step, x["scratch"][2 * c0:2 * (c0 + n)].data_ptr(), x["replica"][c0:c0 + n].data_ptr(),
+                counts.data_ptr(), None if log_alpha is None else log_alpha.data_ptr(), self._stream()))
+        if not whole:
+            x["counts"][:, c0 // m:(c0 + n) // m] += counts
+
+    def exchange_stats(self):
+        """Per lower member a of a pair (a, a + 1), CUDA tensors (M,): `attempts` (pairs of chains tried, m a sweep the pair takes
+        part in), `accepts` (pairs swapped) and `rate` = accepts / attempts (nan for a member that was never the lower one)."""
+        c = self._exchange_buffers()["counts"]
+        return {"attempts": c[0].clone(), "accepts": c[1].clone(), "rate": c[1].double() / c[0].double()}
+
+    def _advance_exchanging(self, n_steps, plan, thin, out, replay, chain_major, row0, keep):
+        """advance() cut at the sweep points.  Rows are kept at the call's steps thin, 2 thin, ..: a piece that starts on one of
+        them keeps whole periods, a piece inside a period keeps its last state if the period ends with it."""
+        R, k = plan
+        if replay is not None:
+            raise ValueError("a TargetBatch runs on the library stream: replay= is not built for it")
+        if thin is not None:
+            thin = int(thin)
+            if thin < 1:
+                raise ValueError("thin must be >= 1")
+            if not keep:
+                raise ValueError("keep=False feeds the running statistics, which a TargetBatch does not have")
+            if k % thin:
+                raise ValueError(f"with kept rows the sweeps fall on kept rows: every ({k}) must be a multiple of thin ({thin})")
+            n_keep = n_steps // thin
+            if not chain_major:
+                if out is None:
+                    out = torch.empty((n_keep, self.d, self.n_chains), dtype=torch.float64, device=self._tdev)
+                elif (tuple(out.shape) != (n_keep, self.d, self.n_chains) or out.dtype != torch.float64 or not out.is_contiguous()):
+                    raise ValueError("out must be a contiguous float64 tensor [n_steps//thin, d, n_chains]")
+        self._exchange_buffers()
+        done = 0
+        while done < n_steps:
+            seg = min(k - self._step % k, n_steps - done)
+            rows, t = 0, None
+            if thin is not None:
+                off = done % thin
+                if off:
+                    seg = min(seg, thin - off)
+                    rows, t = (1, seg) if off + seg == thin else (0, None)
+                elif seg >= thin:
+                    seg -= seg % thin
+                    rows, t = seg // thin, thin
+            if rows:
+                r = done // thin
+                if chain_major:
+                    self.advance(seg, thin=t, out=out, chain_major=True, row0=row0 + r, exchange=False)
+                else:
+                    self.advance(seg, thin=t, out=out[r:r + rows], exchange=False)
+            else:
+                self.advance(seg, exchange=False)
+            done += seg
+            if self._step % k == 0:
+                self._sweep(R, (self._step // k) % 2)
+        return out if thin is not None else None
+
     # ------------------------------------------------------------------ running statistics
     def enable_stats(self, lags=32, projection=None, hop=None, modes=None, second_moment=None):
         """Accumulate running statistics of the retained series inside the sampler kernels (gsss_run_args.stats_dev):
@@ -437,6 +572,8 @@ class RejectionSphericalSliceSampler:
              "sampler": self._sampler, "mode": self.mode}
         if self._rng_state is not None:
             d["rng_state"] = self._rng_state.cpu().numpy().view(np.uint64)
+        if self._xchg is not None:
+            d["exchange"] = {"replica": self._xchg["replica"].cpu().numpy(), "counts": self._xchg["counts"].cpu().numpy()}
         return d
 
     def load_state_dict(self, d):
@@ -454,6 +591,10 @@ class RejectionSphericalSliceSampler:
         if self._rng_state is not None:
             self._rng_state.copy_(torch.from_numpy(np.asarray(d["rng_state"], dtype=np.uint64).view(np.int64)))
             self._sync_rng()
+        if "exchange" in d:
+            x = self._exchange_buffers()
+            x["replica"].copy_(torch.from_numpy(np.asarray(d["exchange"]["replica"], dtype=np.int64)))
+            x["counts"].copy_(torch.from_numpy(np.asarray(d["exchange"]["counts"], dtype=np.int64)))
 
     # ------------------------------------------------------------------ running
     def _launch(self, n_steps, samples=None, thin=1, replay=None, chain_rows=0, samples_ptr=None, stats=False):
@@ -500,7 +641,7 @@ class RejectionSphericalSliceSampler:
         """sample() has allocated its (chains, draws, dims) buffer and filled row 0; the retained rows follow."""
         self._sample_buffer = out
 
-    def advance(self, n_steps, *, thin=None, out=None, replay=None, chain_major=False, row0=0, keep=True):
+    def advance(self, n_steps, *, thin=None, out=None, replay=None, chain_major=False, row0=0, keep=True, exchange=None):
         """Advance every chain by n_steps transitions on the GPU (asynchronously).
 
         thin=None keeps nothing; thin=t >= 1 keeps the state after every t-th step and returns a
@@ -511,10 +652,18 @@ class RejectionSphericalSliceSampler:
         `replay` (n_chains, stride) replays recorded draws instead of the Philox stream.
         keep=False with thin=t stores nothing and only feeds the running statistics (enable_stats) with every
         t-th state; with keep=True they are fed with the very states that are stored.
+        exchange=dict(ladder=R, every=k) (a TargetBatch sampler): replica exchange along ladders of R consecutive members
+        (`exchange()`), a sweep after every global step s with s % k == 0, of parity (s / k) % 2 -- a function of s alone, so
+        that advance(20) equals advance(10); advance(10).  The launches are cut at the sweep points; a kept row is the state
+        BEFORE the sweep that follows its step.  With kept rows k must be a multiple of thin.
         """
         n_steps = int(n_steps)
         if n_steps < 0:
             raise ValueError("n_steps must be >= 0")
+        if exchange is None:
+            exchange = self._exchange_active
+        if exchange:
+            return self._advance_exchanging(n_steps, self._exchange_plan(exchange), thin, out, replay, chain_major, row0, keep)
         if replay is not None and self._batch_m is not None:
             raise ValueError("a TargetBatch runs on the library stream: replay= is not built for it")
         if replay is not None:
@@ -588,7 +737,7 @@ class RejectionSphericalSliceSampler:
         self._sync_rng()
         return self.state
 
-    def sample(self, n_samples, burnin=0, return_all_samples=False, *, thin=1, as_tensor=False, blocks=None):
+    def sample(self, n_samples, burnin=0, return_all_samples=False, *, thin=1, as_tensor=False, blocks=None, exchange=None):
         """Markov chain(s) of the desired size (mcmc.py:55-77): the initial state is row 0 of the
         chain, `n_samples + burnin - 1` transitions are simulated, the first `burnin` rows are
         dropped unless return_all_samples.  One chain -> (n_samples, d); many -> (n_chains, n_samples, d).
@@ -601,7 +750,12 @@ class RejectionSphericalSliceSampler:
         run of the (chains, draws, dims) array -- so that the copy of block k runs under the kernel of block k + 1.  The
         streams are keyed by global chain id (or are one generator per chain): the result does not depend on `blocks`
         (None: chosen from the sizes; 1: one launch sequence for all chains, as `as_tensor=True` always does).
+
+        exchange=dict(ladder=R, every=k): replica exchange as in `advance`; blocks of chains are then runs of whole ladders.
         """
+        if exchange is not None:
+            with self._exchanging(exchange):
+                return self.sample(n_samples, burnin, return_all_samples, thin=thin, as_tensor=as_tensor, blocks=blocks)
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")  # mcmc.py:62
         burnin = determine_burnin(n_samples, burnin)
@@ -619,7 +773,7 @@ class RejectionSphericalSliceSampler:
         return out[0] if self._single else out
 
     def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None,
-                  log_prob=False, lags=None, mixing=False):
+                  log_prob=False, lags=None, mixing=False, exchange=None):
         """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
         would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
         windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
@@ -663,7 +817,14 @@ class RejectionSphericalSliceSampler:
         folds.  The result carries `mix_step`, `mix_counts`, `mix_modes`, `mix_weights`; stats() adds geodesic_step,
         geodesic_step_sd, hop_frequency, mode_occupancy, mode_kl (with weights) and, with transitions=True, mode_transitions
         and mode_switch_frequency (diagnostics.from_target_mixing).  into= continues them with the directions they were begun
-        with, the pair at the seam counted once; a summary begun without mixing cannot take it up."""
+        with, the pair at the seam counted once; a summary begun without mixing cannot take it up.
+
+        exchange=dict(ladder=R, every=k): replica exchange as in `advance`, during burn-in and between the retained draws; k must
+        be a multiple of thin.  With mixing=True this is the remedy for the targets that `hop_frequency == 0` finds."""
+        if exchange is not None:
+            with self._exchanging(exchange):
+                return self.summarize(n_samples, burnin, thin=thin, window=window, second_moment=second_moment,
+                                      chains_per_target=chains_per_target, into=into, log_prob=log_prob, lags=lags, mixing=mixing)
         from . import diagnostics
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")
@@ -842,8 +1003,8 @@ class RejectionSphericalSliceSampler:
             block_s = (skip + (n_rows - 1) * thin) * _ROUND_STEP_S
             blocks = int(min(16, nbytes // (32 << 20), copy_s / max(block_s, 1e-6)))
         blocks = max(1, min(int(blocks), n))
-        if self._batch_m is not None:  # a block of chains is a run of whole targets
-            blocks = min(blocks, n // self._batch_m)
+        if self._batch_m is not None:  # a block of chains is a run of whole targets -- of whole ladders under exchange
+            blocks = min(blocks, n // self._block_unit())
         if blocks > 1 and (not self._blockwise or self._stats is not None):
             raise ValueError("this sampler carries per-chain launch state beyond the slice samplers': blocks must be 1")
         return blocks
@@ -858,11 +1019,14 @@ class RejectionSphericalSliceSampler:
         self._n_reject, self._n_tries, self._err = keep[3][c0:c1], keep[4][c0:c1], keep[5][c0:c1]
         self._rng_state = None if keep[6] is None else keep[6][c0:c1]
         self._step = step
+        first = self._xchg_first
+        self._xchg_first = first + c0
         try:
             yield
             step_end = self._step
         finally:
             (self._state, self.n_chains, self.chain_offset, self._n_reject, self._n_tries, self._err, self._rng_state, self._step) = keep
+            self._xchg_first = first
         self._state[:, c0:c1] = sub
         self._step = step_end
 
@@ -884,8 +1048,8 @@ class RejectionSphericalSliceSampler:
             main.synchronize()
             return host
         per = -(-n // blocks)
-        if self._batch_m is not None:  # cut at multiples of m only
-            per = -(-per // self._batch_m) * self._batch_m
+        if self._batch_m is not None:  # cut at multiples of m only (of R m under exchange)
+            per = -(-per // self._block_unit()) * self._block_unit()
         bufs = [torch.empty((per, n_rows, d), dtype=torch.float64, device=self._tdev) for _ in range(2)]
         copy = torch.cuda.Stream(dev)
         copied = [None, None]                       # the event after which a buffer may be written again

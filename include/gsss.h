@@ -443,6 +443,30 @@ int gsss_target_mixing(const double *ring_dev, int64_t ring_rows, int64_t first_
                        int64_t n_chains, int32_t d, int64_t chains_per_target, const double *dirs_dev, int32_t n_modes,
                        int32_t flags, double *step_dev, int64_t *count_dev, int device, void *stream);
 
+/* Replica exchange (parallel tempering) along ladders of members of a gsss_target_create_batch handle: ONE sweep of one parity
+ * over the chains of a launch.  state_dev is component-major [d][n_chains], chain 0 being the first chain of member `target0`;
+ * m = the handle's chains_per_target.  The n_chains / m members form ladders of `ladder` consecutive members; a sweep of parity p
+ * pairs member a = g ladder + 2 k + p of the call with b = a + 1 for every k with 2 k + p + 1 < ladder, the others sit out.
+ * Chain i of a (column c_a = a m + i) is paired with chain i of b; with l_t member t's log-density (the value of
+ * gsss_batch_logprob, bit for bit), in double precision and in this order,
+ *     log alpha = (l_a(x_b) - l_a(x_a)) + (l_b(x_a) - l_b(x_b)),
+ * and the two columns are swapped iff all four values are finite, err_dev is 0 for both chains, and log(u) < log alpha, u the
+ * first 53-bit uniform of Philox block 0xFFFFFFFF at (seed, chain = chain_offset + c_a, step) -- a block no sampler draws.  u = 0
+ * swaps.  An exchange between two members with their own densities leaves the product law of the batch invariant whatever the
+ * members are.  Only the state columns move, and with them the entries of replica_dev [n_chains] if given; counters and err stay
+ * with the slot.  scratch_dev holds gsss_exchange_scratch_doubles(n_chains) = 2 n_chains doubles (the four values of every pair).
+ * counts_dev, if given, is int64 [2][n_chains / m], ADDED to: per lower member a, the pairs of chains tried (m a sweep it takes
+ * part in, refused pairs included) and the pairs swapped.  log_alpha_out, if given, is [n_chains] and receives log alpha at c_a.
+ * Two launches on `stream`: the members' evaluation in the layout gsss_logprob uses for the shape, then the swap.
+ * GSSS_E_INVALID: ladder < 2, parity outside {0, 1}, negative counts, a target0 that is no multiple of ladder, a NULL handle,
+ * n_chains no multiple of m ladder, a range that reaches past the last member, chain ids or a step beyond the stream's 48 bits,
+ * a NULL state_dev / err_dev / scratch_dev with n_chains > 0; GSSS_E_UNSUPPORTED: a handle that is no batch, more workgroups than
+ * a grid holds -- all before the device is touched.  n_chains = 0 does nothing.  The reference has no replica exchange. */
+int64_t gsss_exchange_scratch_doubles(int64_t n_chains);
+int gsss_batch_exchange(const gsss_target *batch, double *state_dev, const int32_t *err_dev, int64_t n_chains, int64_t target0,
+                        int32_t ladder, int32_t parity, uint64_t seed, uint64_t chain_offset, uint64_t step, double *scratch_dev,
+                        int64_t *replica_dev, int64_t *counts_dev, double *log_alpha_out, void *stream);
+
 /* 1 if gsss_run accepts `mode` for this target's shape (fast mode is built for the shapes listed in
  * geosss_amd/csrc/gsss_fast_*.hip), else 0. */
 int gsss_mode_supported(const gsss_target *t, int32_t mode);
