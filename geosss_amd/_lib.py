@@ -79,6 +79,10 @@ SIGNATURES = {
     "gsss_exchange_scratch_doubles": (C.c_int64, [C.c_int64]),
     "gsss_batch_exchange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_uint64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsss_ladder_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int64]),
+    "gsss_ladder_acc_doubles": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "gsss_batch_ladder": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "gsss_last_launch": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gsss_batch_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

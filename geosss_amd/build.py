@@ -27,7 +27,11 @@ CXXFLAGS += os.environ.get("GSSS_HIPCC_FLAGS", "").split()
 # kernel fits three wavefronts per SIMD without spilling (measured: 156 against 168 + 8 spilled registers).  The option is an
 # internal LLVM one: it is probed once on an empty translation unit and left out if this compiler does not know it (the
 # kernels then spill -- tests/test_abi.py::test_group_kernels_do_not_spill says so instead of a silent 30 GB of scratch traffic).
-OPTIONAL_SOURCE_FLAGS = {"gsss_fast_curvespec.hip": ["-mllvm", "-disable-machine-licm"]}
+# The ladder evaluation (gsss_ladder.hip) loops over the rows of a block around batch_logprob_kernel's body: with the hoisting,
+# the constants of exp / log and the lanes' address offsets stay in registers across the loop and eleven of its thirty builds
+# lose one to three wavefronts per SIMD against the one-row kernel (tests/test_ladder_host.py::test_resource_budget).
+OPTIONAL_SOURCE_FLAGS = {"gsss_fast_curvespec.hip": ["-mllvm", "-disable-machine-licm"],
+                         "gsss_ladder.hip": ["-mllvm", "-disable-machine-licm"]}
 _flag_ok = {}
 
 

@@ -12,6 +12,7 @@
 #include "gsss_batch.h"
 #include "gsss_batch_logprob.h"
 #include "gsss_exchange.h"
+#include "gsss_ladder.h"
 #include "gsss_fast.h"
 #include "gsss_launch.h"
 #include "gsss_mh.h"
@@ -1178,6 +1179,71 @@ int gsss_batch_exchange(const gsss_target *t, double *state_dev, const int32_t *
     a.chain_offset = chain_offset;
     a.step = step;
     return launch_batch_exchange(vec, tbb, a, static_cast<hipStream_t>(stream));
+}
+
+int64_t gsss_ladder_scratch_doubles(int64_t n_rows, int64_t n_chains)
+{
+    if (n_rows < 0 || n_chains < 0) return GSSS_E_INVALID;
+    if (n_rows == 0 || n_chains == 0) return 0;
+    if (n_chains > INT64_MAX / 3 || n_rows > INT64_MAX / (3 * n_chains)) return GSSS_E_INVALID;
+    return 3 * n_rows * n_chains;
+}
+
+int64_t gsss_ladder_acc_doubles(int64_t n_chains, int64_t chains_per_target, int32_t ladder)
+{
+    if (n_chains < 0 || chains_per_target < 1 || ladder < 2) return GSSS_E_INVALID;
+    if (chains_per_target > INT64_MAX / ladder || n_chains % (chains_per_target * ladder) != 0) return GSSS_E_INVALID;
+    if (n_chains > INT64_MAX / kLadderSlots) return GSSS_E_INVALID;
+    return (n_chains / chains_per_target / ladder) * (ladder - 1) * chains_per_target * kLadderSlots;
+}
+
+int gsss_batch_ladder(const gsss_target *t, const double *samples_dev, int64_t n_rows, int64_t n_chains, int64_t target0,
+                      int32_t ladder, double *scratch_dev, double *acc_dev, void *stream)
+{
+    if (ladder < 2) {
+        set_error("gsss_batch_ladder: need ladder >= 2 (ladder = %d)", ladder);
+        return GSSS_E_INVALID;
+    }
+    if (n_rows < 0 || n_chains < 0 || target0 < 0 || target0 % ladder != 0) {
+        set_error("gsss_batch_ladder: n_rows (%lld) and n_chains (%lld) must be >= 0 and target0 (%lld) a multiple of the ladder (%d) "
+                  ">= 0", (long long)n_rows, (long long)n_chains, (long long)target0, ladder);
+        return GSSS_E_INVALID;
+    }
+    if (!t) {
+        set_error("gsss_batch_ladder: null handle");
+        return GSSS_E_INVALID;
+    }
+    if (!is_batch(t)) {
+        set_error("gsss_batch_ladder takes a gsss_target_create_batch handle: a ladder is a run of a batch's members");
+        return GSSS_E_UNSUPPORTED;
+    }
+    const int64_t m = t->batch.m;
+    if (n_chains % (m * ladder) != 0 || target0 > t->batch.n_targets || n_chains / m > t->batch.n_targets - target0) {
+        set_error("gsss_batch_ladder: %lld chains from target %lld on are no run of whole ladders of %d members of the batch (%lld "
+                  "chains per target, %d targets)", (long long)n_chains, (long long)target0, ladder, (long long)m, t->batch.n_targets);
+        return GSSS_E_INVALID;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    if (!samples_dev || !scratch_dev || !acc_dev) {
+        set_error("gsss_batch_ladder: %s is null", !samples_dev ? "samples_dev" : (!scratch_dev ? "scratch_dev" : "acc_dev"));
+        return GSSS_E_INVALID;
+    }
+    const int vec = select_vec_for(t->tb, 0);
+    if (vec < 0) return vec;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return GSSS_E_HIP;
+    TargetBlock tbb = t->tb;
+    tbb.blob += target0 * t->batch.stride;
+    LadderBlock a{};
+    a.x = samples_dev;
+    a.lp3 = scratch_dev;
+    a.acc = acc_dev;
+    a.stride = t->batch.stride;
+    a.n_rows = n_rows;
+    a.n = n_chains;
+    a.m = m;
+    a.R = ladder;
+    return launch_batch_ladder(vec, tbb, a, static_cast<hipStream_t>(stream));
 }
 
 int gsss_run(const gsss_target *t, const gsss_run_args *a, void *stream)

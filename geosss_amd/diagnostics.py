@@ -681,6 +681,114 @@ def from_target_mixing(step, counts, n_modes, *, weights=None):
     return out
 
 
+LADDER_SLOTS = 10  # doubles per pair-chain of gsss_batch_ladder
+
+
+def _ladder_fold(handle, lib, x, n_rows, n, target0, ladder, scratch, acc):
+    """gsss_batch_ladder on the first n_rows rows of the contiguous block x (.., d, n) of the batch handle's members from
+    target0 on; scratch holds 3 n_rows n doubles."""
+    from . import _lib
+    from .sphere import current_stream_ptr
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        _lib.check(lib.gsss_batch_ladder(handle, x.data_ptr(), n_rows, n, target0, ladder, scratch.data_ptr(), acc.data_ptr(),
+                                         current_stream_ptr(dev)))
+
+
+def target_ladder(batch, x, ladder, *, chain_major=False, acc=None):
+    """The sums behind the log normalising constants along ladders of a TargetBatch's members, from draws you hold, on the
+    device and without atomics (gsss_batch_ladder, include/gsss.h).
+
+    x: a CUDA float64 tensor, component-major (rows, d, N) -- what `advance(..., thin=t)` returns -- or, with chain_major=True,
+    (N, rows, d) -- what `sample(..., as_tensor=True)` returns.  The N chains cover all the batch's members, m = N / len(batch)
+    each; the members form G = len(batch) / ladder ladders of R = `ladder` consecutive members, rung r colder than rung r + 1
+    (`TargetBatch.tempered`'s order).  For every pair (a, b = a + 1) of neighbouring rungs and every chain i, each row gives
+    u = l_a(x_b) - l_b(x_b) from the hotter member's draw and v = l_b(x_a) - l_a(x_a) from the colder member's, l_t the
+    members' own `log_prob`, bit for bit; a row is used iff all four values are finite.  Returns, or continues, `acc`
+    (G, R - 1, m, 10): draws used; M_u = max u and S_u = sum exp(u - M_u); sum u, sum u^2; M_v, S_v; sum v, sum v^2; draws
+    skipped.  The result depends on the rows and their order alone: any cut into calls gives the same bits.  x is passed in
+    blocks of rows, so that the scratch (three values per draw) never exceeds the size of x itself.
+    -> `from_target_ladder`."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64 or x.ndim != 3:
+        raise ValueError("x must be a CUDA float64 tensor (rows, d, N), or (N, rows, d) with chain_major=True")
+    N, rows, d = (int(v) for v in (x.shape if chain_major else (x.shape[2], x.shape[0], x.shape[1])))
+    M, R = len(batch), int(ladder)
+    if d != batch.d:
+        raise ValueError(f"the batch's targets live in d={batch.d} (got {d})")
+    if R < 2 or M % R:
+        raise ValueError(f"the {M} targets of the batch are no run of whole ladders of {R} members (ladder >= 2)")
+    if N < M or N % M:
+        raise ValueError(f"the number of chains ({N}) must be a multiple of the batch's {M} targets, with at least one chain each")
+    m = N // M
+    shape = (M // R, R - 1, m, LADDER_SLOTS)
+    if acc is None:
+        acc = torch.zeros(shape, dtype=torch.float64, device=x.device)
+    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != shape or acc.dtype != torch.float64 or acc.device != x.device
+          or not acc.is_contiguous()):
+        raise ValueError(f"acc must be a contiguous float64 tensor {shape} on the device of x")
+    if rows == 0:
+        return acc
+    tgt = batch._device_target(x.device, chains_per_target=m)
+    xc = x.permute(1, 2, 0).contiguous() if chain_major else x.contiguous()
+    per = max(1, min(rows, rows * d // 3))           # 3 per N doubles of scratch <= rows d N
+    scratch = torch.empty(int(tgt.lib.gsss_ladder_scratch_doubles(per, N)), dtype=torch.float64, device=x.device)
+    for r0 in range(0, rows, per):
+        w = min(per, rows - r0)
+        _ladder_fold(tgt.handle, tgt.lib, xc[r0:r0 + w], w, N, 0, R, scratch, acc)
+    return acc
+
+
+def from_target_ladder(acc, *, hot_log_z=None):
+    """Log normalising constants from the accumulators of `target_ladder` / `Sampler.summarize(log_z=)`: acc (G, R - 1, m, 10),
+    pair k of ladder g being the rungs (k, k + 1), rung 0 the coldest.  The per-chain sums are folded over the m chains with
+    logsumexp and sums, where acc lives.  With n = the draws used over the pair's chains, every entry (G, R - 1):
+
+        log_z_ratio_forward  = log( sum_i S_u e^{M_u} / n )      the stepping-stone (free-energy perturbation) estimate of
+                               log Z_a / Z_b from the HOTTER member's draws, E_b[p_a / p_b];
+        log_z_ratio_backward = -log( sum_i S_v e^{M_v} / n )     the same ratio from the colder member's draws, E_a[p_b / p_a];
+        log_z_ratio          = log_z_ratio_forward.
+
+    The forward estimate is the one reported and summed, the backward one a consistency check that is NOT averaged in: the
+    hotter member's draws cover the colder member's mass, so the forward weights are tame, while the colder member's draws
+    rarely reach where the hotter one has its mass and the backward weights are heavy-tailed at the cold end (a Watson target,
+    kappa = 20, d = 5, beta halving, by quadrature: coefficient of variation of a weight 0.3 .. 1.0 forward, up to 5.1
+    backward).
+
+        log_z_lower = mean u,  log_z_upper = -mean v             the Jensen (Gibbs-Bogoliubov) bounds: for the very sample
+                               log_z_lower <= log_z_ratio_forward and log_z_ratio_backward <= log_z_upper hold exactly;
+        log_z_ratio_se       = the standard deviation of the m per-chain forward estimates / sqrt(m): a between-chain standard
+                               error, itself known to a relative sqrt(2 / (m - 1)) (NaN for m = 1);
+        used, skipped        = draws used and skipped, over the pair's chains;
+        log_z (G, R)         = the sum of log_z_ratio from the hottest rung down, the hottest rung being 0, or hot_log_z (a
+                               number or (G,): `TargetBatch.hot_log_z`) where given: log Z of every rung.  A ladder whose
+                               hot_log_z is NaN (its hottest rung is not flat) keeps 0 there: its log_z is log Z relative to
+                               its hottest rung, and differences between rungs are what they are either way.
+
+    CPU or CUDA tensors."""
+    acc = _t(acc).to(torch.float64)
+    if acc.ndim != 4 or acc.shape[-1] != LADDER_SLOTS:
+        raise ValueError("acc must be (G, R - 1, m, 10)")
+    G, m = int(acc.shape[0]), int(acc.shape[2])
+    n_i = acc[..., 0]
+    used, skipped = n_i.sum(-1), acc[..., 9].sum(-1)
+    neg_inf = torch.full_like(n_i, float("-inf"))
+    lse_u = torch.where(n_i > 0, acc[..., 1] + torch.log(acc[..., 2]), neg_inf)   # per chain: log sum exp(u)
+    lse_v = torch.where(n_i > 0, acc[..., 5] + torch.log(acc[..., 6]), neg_inf)
+    forward = torch.logsumexp(lse_u, dim=-1) - torch.log(used)
+    backward = -(torch.logsumexp(lse_v, dim=-1) - torch.log(used))
+    per_chain = lse_u - torch.log(n_i)
+    se = per_chain.std(dim=-1, unbiased=True) / float(np.sqrt(m)) if m > 1 else torch.full_like(forward, float("nan"))
+    hot = torch.zeros(G, dtype=torch.float64, device=acc.device)
+    if hot_log_z is not None:
+        given = torch.as_tensor(hot_log_z, dtype=torch.float64).to(acc.device).reshape(-1)
+        hot = hot + torch.where(torch.isnan(given), torch.zeros_like(given), given)
+    down = torch.flip(torch.cumsum(torch.flip(forward, dims=[1]), dim=1), dims=[1])      # rung r: the pairs r .. R - 2
+    log_z = torch.cat([down, torch.zeros((G, 1), dtype=torch.float64, device=acc.device)], dim=1) + hot[:, None]
+    return {"log_z_ratio_forward": forward, "log_z_ratio_backward": backward, "log_z_ratio": forward,
+            "log_z_lower": acc[..., 3].sum(-1) / used, "log_z_upper": -acc[..., 7].sum(-1) / used, "log_z_ratio_se": se,
+            "used": used, "skipped": skipped, "log_z": log_z}
+
+
 class TargetMoments:
     """What `Sampler.summarize` returns: the per-target accumulators of a run (`acc` (M, rows), `chain_sum` (d, n), device
     tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`.
@@ -701,7 +809,13 @@ class TargetMoments:
     `mix_dirs` (M, 1 + K, d) and whether the transitions are counted, from which into= goes on; without lags `hist` is the one
     last retained row, so that the pair at the seam of two calls counts exactly once.  stats() then adds geodesic_step,
     geodesic_step_sd, hop_frequency, mode_occupancy and, where they apply, mode_transitions, mode_switch_frequency and mode_kl
-    (`from_target_mixing`)."""
+    (`from_target_mixing`).
+
+    With `summarize(log_z=)` also the sums behind the log normalising constants along the ladders of the sampler's members:
+    `ladder` = R, `ladder_acc` (G, R - 1, m, 10) (see `target_ladder`), from which into= goes on, and `ladder_hot_log_z` (G,), the
+    batch's `hot_log_z` (NaN where the hottest rung is not flat).  stats() then adds log_z_ratio (the forward estimate; the
+    backward one is reported beside it as a check, not averaged in), log_z_ratio_forward, log_z_ratio_backward, log_z_lower,
+    log_z_upper, log_z_ratio_se, used, skipped, log_z and hot_log_z (`from_target_ladder`)."""
 
     def __init__(self, acc, chain_sum, d, chains_per_target, second_moment, lp_acc=None, lp_chain_sum=None, lp_best=None,
                  x_best=None):
@@ -711,10 +825,19 @@ class TargetMoments:
         self.lags, self.acov, self.hist, self.lp_acov, self.lp_hist = None, None, None, None, None
         self.mix_step, self.mix_counts, self.mix_modes, self.mix_weights = None, None, None, None
         self.mix_dirs, self.mix_transitions = None, False
+        self.ladder, self.ladder_acc, self._ladder_hot, self._ladder_source = None, None, None, None
 
     @property
     def n_targets(self):
         return int(self.acc.shape[0])
+
+    @property
+    def ladder_hot_log_z(self):
+        """(G,) numpy: `TargetBatch.hot_log_z` of the ladders summarised, taken from the batch when first asked for."""
+        if self._ladder_hot is None and self._ladder_source is not None:
+            batch, g0 = self._ladder_source
+            self._ladder_hot = batch.hot_log_z(self.ladder)[g0:g0 + int(self.ladder_acc.shape[0])]
+        return self._ladder_hot
 
     def update_best(self, values, x):
         """Fold a window into the running best draw: values (w, n) the log_prob of the draws x (w, d, n).  A later draw replaces
@@ -740,6 +863,9 @@ class TargetMoments:
                 out.update({"lp_" + key: val[:, 0] for key, val in lp.items()})
         if self.mix_step is not None:
             out.update(from_target_mixing(self.mix_step, self.mix_counts, self.mix_modes, weights=self.mix_weights))
+        if self.ladder_acc is not None:
+            out.update(from_target_ladder(self.ladder_acc, hot_log_z=self.ladder_hot_log_z))
+            out["hot_log_z"] = torch.as_tensor(self.ladder_hot_log_z, dtype=torch.float64).to(self.ladder_acc.device)
         return out
 
 

@@ -640,6 +640,33 @@ class TargetBatch(Distribution):
         hop = np.array([p.mode for p in self.pdfs], dtype=np.float64)
         return hop, np.zeros((len(self.pdfs), 0, self.d)), None
 
+    def hot_log_z(self, ladder=None):
+        """Per ladder of `ladder` consecutive members (None: the `ladder` set by `tempered`), log of the integral of
+        exp(log_prob) of the HOTTEST member (the ladder's last) over the sphere IF that member's log-density is constant in x,
+        else NaN: -> (G,) numpy.  Constancy is decided from the parameters, not by sampling: a Bingham / BinghamFisher member
+        with A = 0 (and b = 0), a vMF or vMF-mixture member whose every mu = 0 -- what `tempered` gives for beta = 0.  The value
+        is log_prob(e_0) + log(2 pi^{d/2} / Gamma(d/2)), the constant plus the log area of the sphere: what `summarize(log_z=)`
+        adds to the ladder's sums of ratios to give log Z of every rung."""
+        import math
+        R = getattr(self, "ladder", None) if ladder is None else int(ladder)
+        if R is None:
+            raise ValueError("this batch carries no ladder (TargetBatch.tempered sets one): pass ladder=R")
+        M, d = len(self.pdfs), self.d
+        if R < 2 or M % R:
+            raise ValueError(f"the {M} targets of the batch are no run of whole ladders of {R} members (ladder >= 2)")
+        log_area = math.log(2.0) + 0.5 * d * math.log(math.pi) - math.lgamma(0.5 * d)
+        out = np.full(M // R, np.nan)
+        for g in range(M // R):                                   # (the hottest members alone are looked at, and packed if flat)
+            p = self.pdfs[g * R + R - 1]
+            if isinstance(p, Bingham):
+                if not np.any(p.A) and not np.any(getattr(p, "b", 0.0)):
+                    out[g] = 0.0 + log_area                       # log_prob(e_0) = A_00 + b_0
+            elif not any(np.any(q.mu) for q in ([p] if isinstance(p, VonMisesFisher) else [q for q, _ in p._terms()])):
+                logc = np.asarray(p._pack()[4][1], dtype=np.float64).ravel()      # every mu = 0: log_prob = logsumexp_k logc_k
+                top = logc.max()
+                out[g] = top + math.log(float(np.exp(logc - top).sum())) + log_area
+        return out
+
     def _batch_handle(self, device=None):
         """A device copy of the batch for evaluation: any cached one of the device whose parameters are current (the members'
         blobs do not depend on the chains per target), else a new one with one chain per target."""

@@ -353,6 +353,30 @@ class RejectionSphericalSliceSampler:
         c = self._exchange_buffers()["counts"]
         return {"attempts": c[0].clone(), "accepts": c[1].clone(), "rate": c[1].double() / c[0].double()}
 
+    def _ladder_plan(self, log_z, active):
+        """R of summarize(log_z=True | dict(ladder=R)), and the refusals; active: the ladder of exchange=, or None."""
+        if self._batch_m is None:
+            raise ValueError("summarize(log_z=True) evaluates the draws with the batch kernels along ladders of a TargetBatch's "
+                             "members: this sampler holds no TargetBatch (TargetBatch.tempered builds the ladder of one density)")
+        if log_z is True:
+            R = active if active is not None else getattr(getattr(self, "target", None), "ladder", None)
+            if R is None:
+                raise ValueError("log_z=True takes the ladder from exchange= or from the batch (TargetBatch.tempered sets "
+                                 "batch.ladder): neither is there, pass log_z=dict(ladder=R)")
+        elif isinstance(log_z, dict) and set(log_z) == {"ladder"}:
+            R = log_z["ladder"]
+        else:
+            raise ValueError("log_z must be True or dict(ladder=R)")
+        R = int(R)
+        if active is not None and R != active:
+            raise ValueError(f"log_z= and exchange= name different ladders ({R} and {active} members): the ratios are taken "
+                             "between the members that exchange")
+        M = self.n_chains // self._batch_m
+        if R < 2 or M % R or (self.chain_offset // self._batch_m) % R:
+            raise ValueError(f"the {M} targets of this sampler (from target {self.chain_offset // self._batch_m} on) are no run of "
+                             f"whole ladders of {R} members (ladder >= 2)")
+        return R
+
     def _advance_exchanging(self, n_steps, plan, thin, out, replay, chain_major, row0, keep):
         """advance() cut at the sweep points.  Rows are kept at the call's steps thin, 2 thin, ..: a piece that starts on one of
         them keeps whole periods, a piece inside a period keeps its last state if the period ends with it."""
@@ -773,7 +797,7 @@ class RejectionSphericalSliceSampler:
         return out[0] if self._single else out
 
     def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None,
-                  log_prob=False, lags=None, mixing=False, exchange=None):
+                  log_prob=False, lags=None, mixing=False, exchange=None, log_z=False):
         """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
         would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
         windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
@@ -820,11 +844,27 @@ class RejectionSphericalSliceSampler:
         with, the pair at the seam counted once; a summary begun without mixing cannot take it up.
 
         exchange=dict(ladder=R, every=k): replica exchange as in `advance`, during burn-in and between the retained draws; k must
-        be a multiple of thin.  With mixing=True this is the remedy for the targets that `hop_frequency == 0` finds."""
+        be a multiple of thin.  With mixing=True this is the remedy for the targets that `hop_frequency == 0` finds.
+
+        log_z=True or log_z=dict(ladder=R) (a TargetBatch sampler): also the log normalising constants along the ladders of R
+        consecutive members, rung r colder than rung r + 1 (`TargetBatch.tempered`'s order).  Every window, draw 0 included, is
+        passed to gsss_batch_ladder where it lies (two launches: every member evaluated at its own and at its neighbours'
+        columns, then the fold into ten doubles per pair of chains; `diagnostics.target_ladder`).  True takes the ladder from
+        exchange= if given, else from `batch.ladder` (set by `tempered`), else raises ValueError; a ladder that differs from
+        exchange='s is refused.  With exchange= the retained row is the state before the sweep, which has rung r's law either
+        way.  The result carries `ladder`, `ladder_acc` (G, R - 1, m, 10) and `ladder_hot_log_z` (`TargetBatch.hot_log_z`);
+        stats() adds log_z_ratio -- the forward (stepping-stone) estimate from the hotter member's draws; the backward one is
+        reported as a consistency check, not averaged in --, log_z_ratio_forward, log_z_ratio_backward, log_z_lower,
+        log_z_upper, log_z_ratio_se, used, skipped, log_z (G, R) and hot_log_z (`diagnostics.from_target_ladder`).  into=
+        continues the sums; a summary begun without log_z cannot take it up.  The moments, the chains and the other launches
+        are untouched by it."""
         if exchange is not None:
+            if log_z is not None and log_z is not False:      # (refused before the exchange buffers are made)
+                self._ladder_plan(log_z, self._exchange_plan(exchange)[0])
             with self._exchanging(exchange):
                 return self.summarize(n_samples, burnin, thin=thin, window=window, second_moment=second_moment,
-                                      chains_per_target=chains_per_target, into=into, log_prob=log_prob, lags=lags, mixing=mixing)
+                                      chains_per_target=chains_per_target, into=into, log_prob=log_prob, lags=lags, mixing=mixing,
+                                      log_z=log_z)
         from . import diagnostics
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")
@@ -844,6 +884,9 @@ class RejectionSphericalSliceSampler:
         if log_prob and self._batch_m is None:
             raise ValueError("summarize(log_prob=True) evaluates the draws with the batch kernel: wrap the target in a TargetBatch "
                              "of one (TargetBatch([pdf]), chains_per_target = n_chains)")
+        ladder = None
+        if log_z is not None and log_z is not False:
+            ladder = self._ladder_plan(log_z, self._exchange_active[0] if self._exchange_active else None)
         if lags is not None:
             if not 1 <= int(lags) <= 64:
                 raise ValueError(f"lags must be 1 .. 64 (got {lags})")
@@ -891,6 +934,12 @@ class RejectionSphericalSliceSampler:
                 cols = 3 + into.mix_modes + (into.mix_modes ** 2 if into.mix_transitions else 0)
                 into.mix_step = torch.zeros((n // m, 2), dtype=torch.float64, device=self._tdev)
                 into.mix_counts = torch.zeros((n // m, cols), dtype=torch.int64, device=self._tdev)
+            if ladder is not None:
+                g0 = self.chain_offset // m // ladder
+                into.ladder = ladder
+                into.ladder_acc = torch.zeros((n // m // ladder, ladder - 1, m, diagnostics.LADDER_SLOTS), dtype=torch.float64,
+                                              device=self._tdev)
+                into._ladder_source = (self.target, g0)         # (hot_log_z is read from the batch when stats() asks for it)
         elif (into.d != d or into.chains_per_target != m or into.second_moment != full or tuple(into.acc.shape) != (n // m, rows)
               or tuple(into.chain_sum.shape) != (d, n)):
             raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
@@ -902,6 +951,11 @@ class RejectionSphericalSliceSampler:
         elif mix is not None and into.mix_step is None:
             raise ValueError("into= was begun without mixing: the steps and counts of its draws so far were not kept, so it "
                              "cannot take them up")
+        elif ladder is not None and into.ladder != ladder:
+            raise ValueError("into= was begun without log_z along these ladders: the ratios of its draws so far were not kept, so "
+                             "it cannot take them up")
+        ladder = into.ladder
+        lz_scratch = None
         log_prob = into.lp_acc is not None
         mixing = into.mix_step is not None
         L = into.lags or 0
@@ -920,6 +974,8 @@ class RejectionSphericalSliceSampler:
         rows = H + window
         lp_buf = torch.empty((rows, n), dtype=torch.float64, device=self._tdev) if log_prob else None
         buf = torch.empty((rows, d, n), dtype=torch.float64, device=self._tdev) if rest or H else None
+        if ladder is not None:
+            lz_scratch = torch.empty(int(self._lib.gsss_ladder_scratch_doubles(window, n)), dtype=torch.float64, device=self._tdev)
 
         def fold(x, first=0, hist=0):
             """x: a window (w, d, n); with lags it is the rows first .. of the ring, behind `hist` rows of history"""
@@ -940,6 +996,9 @@ class RejectionSphericalSliceSampler:
             if mixing:
                 diagnostics._mixing_fold(buf, first, w, min(1, hist), m, into.mix_dirs, into.mix_modes, into.mix_transitions,
                                          into.mix_step, into.mix_counts)
+            if ladder is not None:
+                diagnostics._ladder_fold(self._target_dev.handle, self._lib, x.contiguous(), w, n, self.chain_offset // m, ladder,
+                                         lz_scratch, into.ladder_acc)
 
         if not H:
             fold(self._state[None])                   # draw 0: the state itself is a (1, d, n) window

@@ -467,6 +467,40 @@ int gsss_batch_exchange(const gsss_target *batch, double *state_dev, const int32
                         int32_t ladder, int32_t parity, uint64_t seed, uint64_t chain_offset, uint64_t step, double *scratch_dev,
                         int64_t *replica_dev, int64_t *counts_dev, double *log_alpha_out, void *stream);
 
+/* Log normalising constants along ladders of members of a gsss_target_create_batch handle: the sums from which the ratios
+ * Z_a / Z_b of neighbouring rungs follow, over a block of retained rows, without stored draws.  samples_dev is component-major
+ * [n_rows][d][n_chains] (as gsss_batch_logprob_draws takes it), chain 0 being the first chain of member `target0`; m = the
+ * handle's chains_per_target.  The n_chains / m members form ladders of `ladder` consecutive members, rung r colder than rung
+ * r + 1; pair (a, b = a + 1) exists for every a that is not the last rung of its ladder.  With l_t member t's log-density (the
+ * value of gsss_batch_logprob, bit for bit) and x_a, x_b chain i of a and of b at one row,
+ *     u = l_a(x_b) - l_b(x_b)   (a draw of the hotter member: E_b[exp u] = Z_a / Z_b)
+ *     v = l_b(x_a) - l_a(x_a)   (a draw of the colder member: E_a[exp v] = Z_b / Z_a)
+ * and the row is used iff all four log-densities are finite, else skipped.
+ * acc_dev [(n_chains / m / ladder) (ladder - 1)][m][10], CONTINUED (zero it before the first block): per pair and chain i
+ *     0      draws used
+ *     1, 2   M_u = the running maximum of u, and S_u = sum exp(u - M_u):  log sum exp(u) = M_u + log S_u
+ *     3, 4   sum u, sum u^2
+ *     5, 6   M_v, S_v
+ *     7, 8   sum v, sum v^2
+ *     9      draws skipped
+ * (M, S) per used draw, in row order:  M' = max(M, u);  S' = S exp(M - M') + exp(u - M'),  from M = -inf, S = 0; the first used
+ * draw (slot 0 is zero) sets M = u, S = 1 directly, so that no -inf - (-inf) is formed and the values of slots 1, 2, 5, 6 before
+ * it are not read.  A pair-chain's slots depend on its own rows in their order alone: a block of 5 rows gives the bits of the
+ * same rows in calls of 3 and 2.  No atomics: the order of every sum is fixed by the arguments.
+ * scratch_dev holds gsss_ladder_scratch_doubles(n_rows, n_chains) = 3 n_rows n_chains doubles (every member's values at its own
+ * and at its two neighbours' columns); gsss_ladder_acc_doubles(n_chains, m, ladder) = (n_chains / m / ladder) (ladder - 1) m 10.
+ * Two launches on `stream`: the members' evaluation in the layout gsss_logprob uses for the shape -- each member's rows staged
+ * once for the whole block --, then the fold.
+ * GSSS_E_INVALID: ladder < 2, negative counts, a target0 that is no multiple of ladder, a NULL handle, n_chains no multiple of
+ * m ladder, a range that reaches past the last member, a NULL samples_dev / scratch_dev / acc_dev with a non-empty block (the two
+ * size functions: a negative count, m < 1, ladder < 2, n_chains no multiple of m ladder, a size beyond 63 bits);
+ * GSSS_E_UNSUPPORTED: a handle that is no batch, more workgroups than a grid holds -- all before the device is touched.
+ * n_rows = 0 or n_chains = 0 does nothing.  The reference has no such estimate. */
+int64_t gsss_ladder_scratch_doubles(int64_t n_rows, int64_t n_chains);
+int64_t gsss_ladder_acc_doubles(int64_t n_chains, int64_t chains_per_target, int32_t ladder);
+int gsss_batch_ladder(const gsss_target *batch, const double *samples_dev, int64_t n_rows, int64_t n_chains, int64_t target0,
+                      int32_t ladder, double *scratch_dev, double *acc_dev, void *stream);
+
 /* 1 if gsss_run accepts `mode` for this target's shape (fast mode is built for the shapes listed in
  * geosss_amd/csrc/gsss_fast_*.hip), else 0. */
 int gsss_mode_supported(const gsss_target *t, int32_t mode);
