@@ -1,7 +1,9 @@
-"""Replica exchange along ladders of a TargetBatch: the reference and the cases (test_exchange_host.py, test_hip_exchange.py).
+"""Replica exchange along ladders of a TargetBatch: the reference and the cases (test_exchange_host.py, test_hip_exchange.py,
+test_exchange_layouts_host.py, test_hip_exchange_layouts.py).
 
 reference_sweep restates one sweep (include/gsss.h, gsss_batch_exchange) in numpy: the members' log-densities from
-reference_math in longdouble, the uniform from the CPU oracle's stream.  Nothing here touches a device.
+reference_math in longdouble, the uniform from the CPU oracle's stream.  Building a case touches no device; check_sweep, which
+the two GPU modules share, holds the device to a case.
 
 THE DECISION MARGIN IS A CONDITION, NOT A MEASUREMENT.  The device forms log alpha from double-precision values and its own
 log(u); a pair whose |log u - log alpha| is at or below MARGIN could be decided either way by the last bits.  Such a pair is left
@@ -81,22 +83,79 @@ SWEEP_R, SWEEP_G = 3, 2       # two ladders of three: one member sits out under 
 SWEEP_SEED, SWEEP_STEP = 777, 40
 # (family, d) of batch_layout_cases, one d per layout family (lane, four, sixteen and sixty-four lanes a chain), and the two
 # batches whose rows stay in global memory
-SWEEP_CASES = [(f, d) for d in (5, 17, 40, 130) for f in ("vmf1", "vmf3", "bingham_dense", "binghamfisher")]
+SWEEP_CASES = [(f, d) for d in (5, 17, 40, 130) for f in ("vmf1", "vmf3", "bingham_dense", "binghamfisher", "bingham_diag")]
 SWEEP_GLOBAL = ["vmf_k7000_d3", "bingham_d129"]
+
+# The layout sweep (test_exchange_layouts_host.py, test_hip_exchange_layouts.py): every one of the fifteen layouts, at the
+# smallest and the largest d of layout_cases.DIMS that the layout serves, one family per target policy (layout_cases.MH_FORCED's
+# choice).  The keys are (family, d) like SWEEP_CASES', so sweep_case serves them as they are.
+LAYOUT_FAMILIES = ("vmf3", "binghamfisher")
+# a flat hottest rung: TargetBatch.tempered(p, FLAT_BETAS) of two members p -- two ladders of three whose last member has every
+# mu = 0 (A = 0 and b = 0); keys ("flat", family, d), one d per layout family
+FLAT_BETAS = (1.0, 0.5, 0.0)
+# non-zero high words of the stream's counter: the second ladder of a SWEEP_CASES case alone, target0 = R.
+# The low words are those of chain_offset = 0 and SWEEP_STEP, so that a sweep that dropped the high words would repeat that
+# sweep's draws -- whose decisions differ (test_exchange_layouts_host.py asserts it on the reference).
+HIGH_KEY = ("vmf3", 5)
+HIGH_CHAIN_OFFSET = 5 << 32
+HIGH_STEP = (0xBEEF << 32) | SWEEP_STEP
+
+
+def case_id(key):
+    return key if isinstance(key, str) else "-".join(map(str, key))
+
+
+@functools.lru_cache(maxsize=None)
+def layout_dims():
+    """For each layout of batch_layout_cases.LAYOUTS the smallest and the largest d of layout_cases.DIMS whose natural layout
+    it is (a lane layout that serves one d of DIMS gives that d once) -> the sorted dims."""
+    import batch_layout_cases as bc
+    by = {}
+    for d in bc.DIMS:
+        by.setdefault(bc.natural_layout(d), []).append(d)
+    assert set(by) == set(bc.LAYOUTS), sorted(set(bc.LAYOUTS) - set(by))
+    return tuple(sorted({d for name in bc.LAYOUTS for d in (min(by[name]), max(by[name]))}))
+
+
+def layout_cases():
+    return [(f, d) for d in layout_dims() for f in LAYOUT_FAMILIES]
+
+
+def flat_dims():
+    """One d per layout family: 5, 17, batch_layout_cases' first d of the sixteen-lane family, 130."""
+    import batch_layout_cases as bc
+    return (5, 17, next(d for d in bc.DIMS if bc.layout_family(bc.natural_layout(d)) == "coop16"), 130)
+
+
+def flat_cases():
+    return [("flat", f, d) for d in flat_dims() for f in LAYOUT_FAMILIES]
+
+
+@functools.lru_cache(maxsize=None)
+def flat_batch(family, d):
+    """TargetBatch.tempered of the first two of batch_layout_cases.members(family, d) along FLAT_BETAS: the batch whose
+    members the ("flat", family, d) cases of this module and of ladder_cases share."""
+    import batch_layout_cases as bc
+    import geosss_amd as gs
+    return gs.TargetBatch.tempered(list(bc.members(family, d)[:SWEEP_G]), FLAT_BETAS)
 
 
 def sweep_members(key):
-    """The 6 members of a sweep case: (family, d) -> batch_layout_cases.members(family, d, 6); a global-row case -> its two
-    members three times over (a ladder of members that differ, twice)."""
+    """The 6 members of a sweep case: (family, d) -> batch_layout_cases.members(family, d, 6); ("flat", family, d) -> the
+    members of flat_batch; a global-row case -> its two members three times over (a ladder of members that differ, twice)."""
     import batch_layout_cases as bc
     if isinstance(key, str):
         a, b = bc.global_members(key)
         return (a, b, a, b, a, b)
+    if key[0] == "flat":
+        return tuple(flat_batch(*key[1:]).pdfs)
     return bc.members(key[0], key[1], SWEEP_R * SWEEP_G)
 
 
 def sweep_m(key):
     import batch_layout_cases as bc
+    if not isinstance(key, str) and key[0] == "flat":
+        return bc.chains_per_target(bc.natural_layout(key[2]))
     if isinstance(key, str):
         import geosss_amd  # noqa: F401  (the members are the package's objects)
         pdfs = bc.global_members(key)
@@ -125,6 +184,92 @@ def sweep_case(key):
     x[4 * m + 1, d // 2] = np.nan       # ladder 1, member 1
     refs = tuple(reference_sweep(pdfs, x, err, m, SWEEP_R, p, SWEEP_SEED, SWEEP_STEP) for p in (0, 1))
     return pdfs, m, x, err, refs
+
+
+@functools.lru_cache(maxsize=None)
+def high_case():
+    """The second ladder of sweep_case(HIGH_KEY) alone -> (all 6 members, m, its rows (3 m, d), its err (3 m,), the reference
+    sweeps of parity 0 and 1 at chain_offset = HIGH_CHAIN_OFFSET and step = HIGH_STEP, the same at chain_offset = 0 and
+    SWEEP_STEP).  The ladder holds the case's NaN column (member 1, chain 1) and no error bit."""
+    pdfs, m, x, err, _ = sweep_case(HIGH_KEY)
+    n = SWEEP_R * m
+    sub, sub_err = x[n:].copy(), err[n:].copy()
+    high = tuple(reference_sweep(pdfs[SWEEP_R:], sub, sub_err, m, SWEEP_R, p, SWEEP_SEED, HIGH_STEP, chain_offset=HIGH_CHAIN_OFFSET)
+                 for p in (0, 1))
+    low = tuple(reference_sweep(pdfs[SWEEP_R:], sub, sub_err, m, SWEEP_R, p, SWEEP_SEED, SWEEP_STEP) for p in (0, 1))
+    return pdfs, m, sub, sub_err, high, low
+
+
+def release():
+    """Drop every cached case (dense members at d >= 1025 are 33 MB each) and batch_layout_cases' with them."""
+    import batch_layout_cases as bc
+    for cache in (sweep_case, high_case, flat_batch):
+        cache.cache_clear()
+    bc.release()
+
+
+# ------------------------------------------------------------------------------------------ one sweep on the device: the checks
+# (check_sweep and log_prob_pairs are the functions of this module that touch a device; test_hip_exchange.py and
+# test_hip_exchange_layouts.py share them)
+def log_prob_pairs(batch, x, m, lower):
+    """The four values of every pair from TargetBatch.log_prob: own[c] = l_t(x_c), and across[c] = l_t(x_partner(c))."""
+    M, d = len(batch), x.shape[1]
+    xm = x.reshape(M, m, d)
+    own = batch.log_prob(xm)
+    partner = np.arange(M)
+    lo = np.flatnonzero(lower.reshape(M, m)[:, 0])
+    partner[lo], partner[lo + 1] = lo + 1, lo
+    across = batch.log_prob(xm[partner])
+    return own.reshape(-1), across.reshape(-1)
+
+
+def check_sweep(key):
+    """One sweep of either parity of sweep_case(key) on the device against reference_sweep: log alpha (the stated combination
+    of TargetBatch.log_prob values bit for bit, the reference's to 1e-10 of the pair's scale, written at the lower chains only),
+    the permuted rows bit for bit, replica, counts; errors and try counts untouched.  -> per parity dict(la: the device's
+    log alpha (n,), own, across: log_prob_pairs' values, rel: the worst deviation of log alpha from the reference)."""
+    import geosss_amd as gs
+    import torch
+    pdfs, m, x, err, refs = sweep_case(key)
+    n = len(x)
+    out = []
+    for parity, ref in enumerate(refs):
+        assert ref["margin"].min() > MARGIN
+        s = gs.ShrinkageSphericalSliceSampler(gs.TargetBatch(list(pdfs)), x, seed=SWEEP_SEED, mode="exact", step_offset=SWEEP_STEP)
+        s._err.copy_(torch.from_numpy(err))
+        before = s.state_rows().cpu().numpy()
+        assert np.array_equal(before, x, equal_nan=True)
+        log_alpha = torch.full((n,), 7.25, dtype=torch.float64, device="cuda")
+        s.exchange(SWEEP_R, parity, log_alpha=log_alpha)
+        after = s.state_rows().cpu().numpy()
+        la = log_alpha.cpu().numpy()
+        lower, swap = ref["lower"], ref["swap"]
+        # log alpha: the stated combination of TargetBatch.log_prob values bit for bit, the reference's to 1e-10 of their scale
+        own, across = log_prob_pairs(s.target, x, m, lower)
+        lo = np.flatnonzero(lower)
+        with np.errstate(invalid="ignore"):
+            want = (across[lo] - own[lo]) + (across[lo + m] - own[lo + m])
+        assert np.array_equal(la[lo], want, equal_nan=True)
+        assert np.all(la[~lower] == 7.25)                                        # written at the lower chains only
+        fin = np.isfinite(ref["log_alpha"][lo].astype(np.float64))
+        rel = np.abs(la[lo][fin] - ref["log_alpha"][lo][fin]).astype(np.float64) / ref["scale"][lo][fin]
+        print(f"{case_id(key)} parity {parity}: {int(swap.sum())} of {int(lower.sum())} swap, log alpha within {rel.max():.1e}, "
+              f"margin {ref['margin'].min():.1e}")
+        assert rel.max() < 1e-10
+        # decisions: a swapped column is the partner's old column bit for bit, every other column is untouched bit for bit
+        # (members that sit out, the pair with the error bit, the pair with the NaN column, pairs the draw refused)
+        moved = np.any((after != before) & ~(np.isnan(after) & np.isnan(before)), axis=1)
+        assert np.array_equal(after, ref["x"], equal_nan=True)
+        assert np.array_equal(after, before[ref["replica"]], equal_nan=True)
+        assert not moved[~(np.isin(np.arange(n), lo[swap[lo]]) | np.isin(np.arange(n), lo[swap[lo]] + m))].any()
+        assert np.array_equal(s.replica.cpu().numpy(), ref["replica"])
+        st = s.exchange_stats()
+        assert np.array_equal(st["attempts"].cpu().numpy(), ref["attempts"]) and np.array_equal(st["accepts"].cpu().numpy(), ref["accepts"])
+        assert not swap[1 * m + 2] and not swap[0 * m + 2] and not swap[4 * m + 1] and not swap[3 * m + 1]   # err, NaN
+        # counters and errors stay with the slot
+        assert np.array_equal(s.errors, err) and not s.n_tries_per_chain.any()
+        out.append({"la": la, "own": own, "across": across, "rel": float(rel.max())})
+    return out
 
 
 # ------------------------------------------------------------------------------------------ the d = 10 ladder

@@ -1,10 +1,13 @@
 """Log normalising constants along ladders of a TargetBatch (gsss_batch_ladder; diagnostics.target_ladder, from_target_ladder,
-summarize(log_z=)): the cases and the host restatement (test_ladder_host.py, test_hip_ladder.py).  Nothing here touches a device.
+summarize(log_z=)): the cases and the host restatement (test_ladder_host.py, test_hip_ladder.py, test_exchange_layouts_host.py,
+test_hip_exchange_layouts.py).  Building a case touches no device; check_accumulators, which the two GPU modules share, holds
+the device to a case.
 
 The cases: two ladders of R = 3 -- the middle rung has both neighbours, the end rungs one -- of M = 6 members that really differ
 (batch_layout_cases.members; a global-row case: its two members three times over), at the smallest shapes that reach every code
 path of the evaluation kernel: a full chunk, a ragged chunk and a workgroup boundary inside every member, in each of the four
-layout families and with the rows in global memory.
+layout families and with the rows in global memory; the layout sweep (both ends of every one of the fifteen layouts) and the
+tempered ladders with a flat hottest rung share exchange_cases' dims and members.
 
 The restatement: the fold of include/gsss.h (gsss_batch_ladder) and the estimators of diagnostics.from_target_ladder in
 np.longdouble, from a table of log-densities.  host_fold walks the rows with the stated recurrence; direct_sums takes the same
@@ -19,8 +22,9 @@ LD = np.longdouble
 SLOTS = 10
 R, G = 3, 2
 N_ROWS = 5
-FAMILIES = ("vmf1", "vmf3", "bingham_dense", "binghamfisher")
+FAMILIES = ("vmf1", "vmf3", "bingham_dense", "binghamfisher", "bingham_diag")
 GLOBAL = "bingham_d129"      # dense Bingham d = 129: d^2 doubles exceed a workgroup's rows, read from global memory
+TOL = 1e-10     # device against host, the project's tolerance (batch_layout_cases.TOL): only exp differs
 
 
 def _coop16_d():
@@ -39,8 +43,21 @@ def cases():
     return [(f, name) for name in ("lane", "coop4", "coop16", "coop64") for f in FAMILIES] + [GLOBAL]
 
 
+def layout_cases():
+    """The layout sweep, ("layout", family, d): exchange_cases' dims (both ends of every one of the fifteen layouts) and
+    families (one per target policy)."""
+    import exchange_cases as ec
+    return [("layout", f, d) for d in ec.layout_dims() for f in ec.LAYOUT_FAMILIES]
+
+
+def flat_cases():
+    """("flat", family, d): exchange_cases.flat_batch, two tempered ladders of three whose hottest rung is flat."""
+    import exchange_cases as ec
+    return [("flat", f, d) for d in ec.flat_dims() for f in ec.LAYOUT_FAMILIES]
+
+
 def case_id(key):
-    return key if isinstance(key, str) else f"{key[0]}-{key[1]}"
+    return key if isinstance(key, str) else "-".join(map(str, key))
 
 
 def case_members(key):
@@ -48,10 +65,18 @@ def case_members(key):
     if isinstance(key, str):
         a, b = bc.global_members(key)
         return (a, b, a, b, a, b)
+    if key[0] == "flat":
+        import exchange_cases as ec
+        return tuple(ec.flat_batch(*key[1:]).pdfs)
+    if key[0] == "layout":
+        return bc.members(key[1], key[2], R * G)
     return bc.members(key[0], shapes()[key[1]][0], R * G)
 
 
 def case_m(key):
+    import batch_layout_cases as bc
+    if not isinstance(key, str) and len(key) == 3:
+        return bc.chains_per_target(bc.natural_layout(key[2]))
     return 7 if isinstance(key, str) else shapes()[key[1]][1]
 
 
@@ -62,7 +87,7 @@ def case_rows(key):
     import batch_layout_cases as bc
     pdfs, m = case_members(key), case_m(key)
     d = pdfs[0].d
-    if not isinstance(key, str):     # the shape is the one that puts the case into its layout family
+    if not isinstance(key, str) and len(key) == 2:     # the shape is the one that puts the case into its layout family
         assert bc.layout_family(bc.layout_of((key[0], d, R * G))) == key[1] and bc.chains_per_target(bc.layout_of((key[0], d, R * G))) == m
     rng = lc._rng("ladder", case_id(key))
     centre = lc._unit(rng.standard_normal(d))
@@ -172,3 +197,70 @@ def synthetic_table(seed, rows=40, ladders=2, ladder=4, m=5):
         lp3[:, g * ladder, :, 1] = np.nan
         lp3[:, g * ladder + ladder - 1, :, 2] = np.nan
     return lp3
+
+
+def release():
+    """Drop every cached case, and exchange_cases' and batch_layout_cases' with them."""
+    import exchange_cases as ec
+    case_rows.cache_clear()
+    ec.release()
+
+
+# ------------------------------------------------------------------------------------------ device against host restatement
+# (device_rows, table and check_accumulators are the functions of this module that touch a device; test_hip_ladder.py and
+# test_hip_exchange_layouts.py share them)
+def device_rows(x):
+    """(rows, N, d) numpy -> the component-major (rows, d, N) CUDA tensor"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(np.transpose(x, (0, 2, 1)))).cuda()
+
+
+def table(batch, x, m, ladder):
+    """lp3 (rows, M, m, 3) from TargetBatch.log_prob: every member at its own rows, at its lower neighbour's and at its upper
+    neighbour's, re-indexed; NaN where the neighbour does not exist (never read)."""
+    rows, N, d = x.shape
+    M = N // m
+    xm = np.ascontiguousarray(x.reshape(rows, M, m, d).transpose(1, 0, 2, 3)).reshape(M, rows * m, d)
+    t = np.arange(M)
+    out = np.full((rows, M, m, 3), np.nan)
+    for w, src, exists in ((0, t, np.ones(M, bool)), (1, t - 1, t % ladder != 0), (2, t + 1, t % ladder != ladder - 1)):
+        lp = batch.log_prob(np.ascontiguousarray(xm[np.where(exists, src, t)])).reshape(M, rows, m).transpose(1, 0, 2)
+        out[..., w][:, exists] = lp[:, exists]
+    return out
+
+
+def rel(got, want):
+    got, want = np.asarray(got, dtype=LD), np.asarray(want, dtype=LD)
+    return float(np.max(np.abs(got - want) / np.maximum(1, np.abs(want))))
+
+
+def check_accumulators(key):
+    """diagnostics.target_ladder on case_rows(key) against host_fold fed with TargetBatch.log_prob's values of the same rows:
+    the counts (slots 0 and 9) equal, every row used, the four plain sums and the two S e^M products within TOL, and
+    chain_major=True the same bits.  -> (the accumulators as a CUDA tensor, {quantity: worst deviation})."""
+    import geosss_amd as gs
+    import torch
+    from geosss_amd import diagnostics
+    pdfs, m, x = case_rows(key)
+    batch = gs.TargetBatch(list(pdfs))
+    acc = diagnostics.target_ladder(batch, device_rows(x), R)
+    assert tuple(acc.shape) == (G, R - 1, m, 10) and acc.is_cuda
+    got = acc.cpu().numpy()
+    want = host_fold(table(batch, x, m, R), R)
+    assert np.array_equal(got[..., 0], want[..., 0]) and np.array_equal(got[..., 9], want[..., 9])
+    assert np.all(got[..., 0] == N_ROWS) and not got[..., 9].any()
+    worst = {}
+    for name, i in (("sum u", 3), ("sum u^2", 4), ("sum v", 7), ("sum v^2", 8)):
+        worst[name] = rel(got[..., i], want[..., i])
+    for name, (iM, iS) in (("S e^M (u)", (1, 2)), ("S e^M (v)", (5, 6))):
+        g = got[..., iS].astype(LD) * np.exp(got[..., iM].astype(LD))
+        w = want[..., iS] * np.exp(want[..., iM])
+        assert np.all(np.isfinite(w)) and np.all(w > 0)
+        worst[name] = float(np.max(np.abs(g - w) / w))
+    print(case_id(key), {k: f"{v:.1e}" for k, v in worst.items()}, "max |u|", float(np.max(np.abs(got[..., 1]))))
+    assert max(worst.values()) < TOL, worst
+    # chain_major: the same draws as (N, rows, d), the same bits
+    again = diagnostics.target_ladder(batch, torch.from_numpy(np.ascontiguousarray(np.transpose(x, (1, 0, 2)))).cuda(), R,
+                                      chain_major=True)
+    assert torch.equal(acc, again)
+    return acc, worst

@@ -20,58 +20,11 @@ def _sampler(pdfs, x, seed, mode="exact", step=0, cls=None, **kw):
     return cls(gs.TargetBatch(list(pdfs)), x, seed=seed, mode=mode, step_offset=step, **kw)
 
 
-def _log_prob_pairs(batch, x, m, lower):
-    """The four values of every pair from TargetBatch.log_prob: own[c] = l_t(x_c), and across[c] = l_t(x_partner(c))."""
-    M, d = len(batch), x.shape[1]
-    xm = x.reshape(M, m, d)
-    own = batch.log_prob(xm)
-    partner = np.arange(M)
-    lo = np.flatnonzero(lower.reshape(M, m)[:, 0])
-    partner[lo], partner[lo + 1] = lo + 1, lo
-    across = batch.log_prob(xm[partner])
-    return own.reshape(-1), across.reshape(-1)
-
-
 # ------------------------------------------------------------------------------------------ one sweep
 @pytest.mark.parametrize("key", ec.SWEEP_CASES + ec.SWEEP_GLOBAL, ids=lambda k: k if isinstance(k, str) else f"{k[0]}-{k[1]}")
 def test_one_sweep_against_the_reference(key):
-    pdfs, m, x, err, refs = ec.sweep_case(key)
-    n, M = len(x), len(pdfs)
-    for parity, ref in enumerate(refs):
-        assert ref["margin"].min() > ec.MARGIN
-        s = _sampler(pdfs, x, ec.SWEEP_SEED, step=ec.SWEEP_STEP)
-        s._err.copy_(torch.from_numpy(err))
-        before = s.state_rows().cpu().numpy()
-        assert np.array_equal(before, x, equal_nan=True)
-        log_alpha = torch.full((n,), 7.25, dtype=torch.float64, device="cuda")
-        s.exchange(ec.SWEEP_R, parity, log_alpha=log_alpha)
-        after = s.state_rows().cpu().numpy()
-        la = log_alpha.cpu().numpy()
-        lower, swap = ref["lower"], ref["swap"]
-        # log alpha: the stated combination of TargetBatch.log_prob values bit for bit, the reference's to 1e-10 of their scale
-        own, across = _log_prob_pairs(s.target, x, m, lower)
-        lo = np.flatnonzero(lower)
-        with np.errstate(invalid="ignore"):
-            want = (across[lo] - own[lo]) + (across[lo + m] - own[lo + m])
-        assert np.array_equal(la[lo], want, equal_nan=True)
-        assert np.all(la[~lower] == 7.25)                                        # written at the lower chains only
-        fin = np.isfinite(ref["log_alpha"][lo].astype(np.float64))
-        rel = np.abs(la[lo][fin] - ref["log_alpha"][lo][fin]).astype(np.float64) / ref["scale"][lo][fin]
-        print(f"{key} parity {parity}: {int(swap.sum())} of {int(lower.sum())} swap, log alpha within {rel.max():.1e}, "
-              f"margin {ref['margin'].min():.1e}")
-        assert rel.max() < 1e-10
-        # decisions: a swapped column is the partner's old column bit for bit, every other column is untouched bit for bit
-        # (members that sit out, the pair with the error bit, the pair with the NaN column, pairs the draw refused)
-        moved = np.any((after != before) & ~(np.isnan(after) & np.isnan(before)), axis=1)
-        assert np.array_equal(after, ref["x"], equal_nan=True)
-        assert np.array_equal(after, before[ref["replica"]], equal_nan=True)
-        assert not moved[~(np.isin(np.arange(n), lo[swap[lo]]) | np.isin(np.arange(n), lo[swap[lo]] + m))].any()
-        assert np.array_equal(s.replica.cpu().numpy(), ref["replica"])
-        st = s.exchange_stats()
-        assert np.array_equal(st["attempts"].cpu().numpy(), ref["attempts"]) and np.array_equal(st["accepts"].cpu().numpy(), ref["accepts"])
-        assert not swap[1 * m + 2] and not swap[0 * m + 2] and not swap[4 * m + 1] and not swap[3 * m + 1]   # err, NaN
-        # counters and errors stay with the slot
-        assert np.array_equal(s.errors, err) and not s.n_tries_per_chain.any()
+    """exchange_cases.check_sweep: log alpha, decisions, permuted rows, replica and counts of both parities."""
+    ec.check_sweep(key)
 
 
 def test_identical_members_always_swap():

@@ -17,58 +17,15 @@ from geosss_amd import diagnostics
 pytestmark = pytest.mark.gpu
 
 LD = np.longdouble
-TOL = 1e-10     # device against host, the project's tolerance (batch_layout_cases.TOL): only exp differs
-
-
-def _device_rows(x):
-    """(rows, N, d) numpy -> the component-major (rows, d, N) CUDA tensor"""
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(x, (0, 2, 1)))).cuda()
-
-
-def _table(batch, x, m, ladder):
-    """lp3 (rows, M, m, 3) from TargetBatch.log_prob: every member at its own rows, at its lower neighbour's and at its upper
-    neighbour's, re-indexed; NaN where the neighbour does not exist (never read)."""
-    rows, N, d = x.shape
-    M = N // m
-    xm = np.ascontiguousarray(x.reshape(rows, M, m, d).transpose(1, 0, 2, 3)).reshape(M, rows * m, d)
-    t = np.arange(M)
-    out = np.full((rows, M, m, 3), np.nan)
-    for w, src, exists in ((0, t, np.ones(M, bool)), (1, t - 1, t % ladder != 0), (2, t + 1, t % ladder != ladder - 1)):
-        lp = batch.log_prob(np.ascontiguousarray(xm[np.where(exists, src, t)])).reshape(M, rows, m).transpose(1, 0, 2)
-        out[..., w][:, exists] = lp[:, exists]
-    return out
-
-
-def _rel(got, want):
-    got, want = np.asarray(got, dtype=LD), np.asarray(want, dtype=LD)
-    return float(np.max(np.abs(got - want) / np.maximum(1, np.abs(want))))
+_device_rows = lz.device_rows
 
 
 # ------------------------------------------------------------------------------------------ device against host restatement
 @pytest.mark.parametrize("key", lz.cases(), ids=lz.case_id)
 def test_accumulators_against_the_host_restatement(key):
-    pdfs, m, x = lz.case_rows(key)
-    batch = gs.TargetBatch(list(pdfs))
-    acc = diagnostics.target_ladder(batch, _device_rows(x), lz.R)
-    assert tuple(acc.shape) == (lz.G, lz.R - 1, m, 10) and acc.is_cuda
-    got = acc.cpu().numpy()
-    want = lz.host_fold(_table(batch, x, m, lz.R), lz.R)
-    assert np.array_equal(got[..., 0], want[..., 0]) and np.array_equal(got[..., 9], want[..., 9])
-    assert np.all(got[..., 0] == lz.N_ROWS) and not got[..., 9].any()
-    worst = {}
-    for name, i in (("sum u", 3), ("sum u^2", 4), ("sum v", 7), ("sum v^2", 8)):
-        worst[name] = _rel(got[..., i], want[..., i])
-    for name, (iM, iS) in (("S e^M (u)", (1, 2)), ("S e^M (v)", (5, 6))):
-        g = got[..., iS].astype(LD) * np.exp(got[..., iM].astype(LD))
-        w = want[..., iS] * np.exp(want[..., iM])
-        assert np.all(np.isfinite(w)) and np.all(w > 0)
-        worst[name] = float(np.max(np.abs(g - w) / w))
-    print(lz.case_id(key), {k: f"{v:.1e}" for k, v in worst.items()}, "max |u|", float(np.max(np.abs(got[..., 1]))))
-    assert max(worst.values()) < TOL, worst
-    # chain_major: the same draws as (N, rows, d), the same bits
-    again = diagnostics.target_ladder(batch, torch.from_numpy(np.ascontiguousarray(np.transpose(x, (1, 0, 2)))).cuda(), lz.R,
-                                      chain_major=True)
-    assert torch.equal(acc, again)
+    """ladder_cases.check_accumulators: the counts equal, the six quantities within ladder_cases.TOL (1e-10, device against
+    host: only exp differs), chain_major the same bits."""
+    lz.check_accumulators(key)
 
 
 SHARED = [("vmf3", "lane"), ("binghamfisher", "coop16"), lz.GLOBAL]

@@ -3,6 +3,7 @@ gradient the reference project recorded, the registration targets' included -- t
 sweep of the layout tests and over the registration cases (tests/registration_cases.py), and its own longdouble arithmetic
 against mpmath at 50 digits.  CPU only.  The last tests evaluate, with the reference alone, the conditions the GPU modules assert
 of their cases: the try margins of the reference chains and the curve's near-ties."""
+import math
 import os
 
 import mpmath
@@ -242,6 +243,42 @@ def test_longdouble_against_mpmath(family, d):
             worst_gr = max(worst_gr, float(max(abs(_mp(a) - b) for a, b in zip(gr[i], gr_mp[i])) / scale))
     print(f"{family} d={d}: longdouble against mpmath {worst_lp:.1e} (log_prob) {worst_gr:.1e} (gradient)")
     assert worst_lp <= 1e-17 and worst_gr <= 1e-17
+
+
+@pytest.mark.parametrize("family", ["vmf1", "vmf3", "bingham_dense", "binghamfisher"])
+@pytest.mark.parametrize("d", [2, 5, 17, 130])
+def test_flat_member_against_the_closed_form(family, d):
+    """The member TargetBatch.tempered gives for beta = 0 (every mu = 0; A = 0 and b = 0), which the documented formulas cover
+    as they stand: kappa -> 0 takes the vMF term's -log(2 pi) - log I0(kappa) to -log(2 pi), and x^T 0 x + 0^T x = 0.  The
+    library's vMF constant is the reference's, the circle's in every dimension: the closed form of a flat mixture is
+    -log(2 pi) + log(sum of the weights as MixtureModel._pack takes them), which is -log area(S^(d-1)) + log sum w at d = 2;
+    a flat Bingham or Fisher-Bingham member is 0.  Both paths (longdouble, mpmath), points on and off the sphere."""
+    import batch_layout_cases as bc
+    import geosss_amd as gs
+    flat = gs.TargetBatch.tempered(bc.members(family, d)[0], [1.0, 0.5, 0.0]).pdfs[2]
+    X = bc.points("flat", 1, 9, d)[0]
+    P = np.concatenate([X, lc.OFF_SPHERE * X[:3]])
+    if family.startswith("vmf"):
+        w = np.array([v for _, v in flat._terms()], dtype=np.float64) if family == "vmf3" else np.ones(1)
+        assert not any(np.any(p.mu) for p in (flat.pdfs if family == "vmf3" else [flat]))
+        with mpmath.workdps(rm.MP_DIGITS):
+            log_2pi = rm._ld(mpmath.log(2 * mpmath.pi))
+        want = -log_2pi + np.log(np.sum(w.astype(rm.LD)))
+        # the reference normalises the weights once more, in longdouble: its sum is 1 where the doubles' is within K 2^-53 of 1
+        bar = 0.0 if family == "vmf1" else 1e-15
+        if d == 2:
+            log_area = np.log(2.0) + 0.5 * d * np.log(np.pi) - math.lgamma(0.5 * d)
+            assert abs(float(want) - np.log(float(np.sum(w))) + log_area) < 1e-15
+    else:
+        assert not np.any(flat.A) and not np.any(getattr(flat, "b", 0.0))
+        want, bar = rm.LD(0), 0.0
+    lp, gr = rm.log_prob_and_gradient(flat, P)
+    assert lp.shape == (12,) and np.all(np.abs(lp - want) <= bar), (lp, want)
+    assert np.all(lp == lp[0]) and not np.any(gr)           # one value at every point, and no slope
+    with mpmath.workdps(rm.MP_DIGITS):
+        for v in rm.log_prob_mp(flat, P[:4]):
+            assert abs(v - _mp(want)) <= max(bar, 1e-17)
+    assert float(rm.log_prob(flat, P[0])) == float(lp[0])
 
 
 # ------------------------------------------------------------------------------------------ the GPU modules' case conditions
