@@ -11,144 +11,46 @@
 // index is a constant: the row loop is unrolled LC times and slot u is written in the u-th of them.  A group holds 2 LC sums
 // (C and Q), the LC ring values and the LC (2 LC for g > 0) values of the rows in flight -- two operations per (value, lag);
 // nothing goes to scratch.  Group 0 also keeps lag 0.
-// Chunks of chains are cut at target boundaries as gsss_moments.hip cuts them: with m <= CW a workgroup takes floor(CW / m) whole
-// targets, otherwise a target takes ceil(m / CW) workgroups.
+// The cut of the chains at target boundaries and the split of the rows over workgroups are gsss_target_fold.h's, with CW as
+// above and the d series as its series.
 //
 // The block's ends.  A row before the history reads as 0, which leaves C_l and Q_l exact.  P_l takes x_r only where r - l is a
 // row that exists: from the first run of LC rows in which that holds for every lag of the group, the lags share ONE sum; the
 // runs before it (the first L - n_hist rows of a series at most) are walked a second time, backwards, for P_l lag by lag,
 // which waits in LDS until the fold adds the shared sum to it.
 //
-// Summation order (fixed by the arguments alone, no atomics: a call's result is the same bits every time).
-//   1. a lane adds its chain's rows in row order (the lag-by-lag part of P_l in reverse row order, then the shared sum);
-//   2. the lanes of a wavefront are combined by a SEGMENTED shuffle reduction (offsets 1, 2, .. 32; a lane adds its neighbour
-//      only if that neighbour belongs to the same target), which leaves a target's sum in the first of its lanes;
-//   3. the wavefronts a target spans are added in wavefront order through LDS by one thread per target;
-//   4. where a target has a single partial (m <= CW and the rows are not split over workgroups) that thread adds it to acc --
-//      all its lags at the end, so that their loads of acc are in flight together --; otherwise the partials go to a workspace
-//      and a second kernel adds them per target in (row split, chunk) order.
-// The rows are split over workgroups only when chains x series give fewer than kWantGrid workgroups; a workgroup that starts
-// inside the block takes its delay line from the block's earlier rows.
+// Summation order: gsss_target_fold.h's steps 1 - 4.  What this unit adds to them: in step 1 the lag-by-lag part of P_l is added
+// in REVERSE row order, then the shared sum is added to it; in step 4 a thread adds a single partial to acc for all its lags at
+// the end, so that their loads of acc are in flight together.  A workgroup that starts inside the block takes its delay line
+// from the block's earlier rows.
 #include "gsss_autocov.h"
-#include "gsss_launch.h"
+#include "gsss_target_fold.h"
 
 namespace gsss {
 namespace {
 
-constexpr int kWantGrid = 1024;  // workgroups below which the rows are split as well
 constexpr int kMinSplitRows = 32;
 
 struct AutocovBlock {
     const double *x;
     int64_t sr, sj;  // doubles from row to row, series to series (the chains of a (row, series) are contiguous)
-    int64_t ring_rows, first_row, n_rows, n_hist;
-    int64_t n, m, n_targets, n_chunks;
-    int32_t d, n_lags, na, rsplit;
-    int32_t tpw;     // targets a workgroup takes (m <= CW), else 0
-    int32_t cpt;     // workgroups a target takes (m > CW), else 0
+    int64_t ring_rows, first_row, n_hist;
+    TargetCut cut;   // series: d
+    int32_t n_lags, na;
     double *acc;
-    double *ws;      // NULL: a target has one partial, added to acc directly; else [rsplit][d][n_chunks][max(tpw, 1)][na]
+    double *ws;      // NULL: a target has one partial, added to acc directly; else the workspace of partials_of
 };
-
-struct Chunk {
-    int64_t c0, t0;  // first chain, first target
-    int32_t nc, nt;  // chains, targets
-    int32_t m_loc;   // chains per target within the chunk
-    int64_t r0, r1;  // rows, relative to the block's first
-    int32_t j;       // series
-};
-
-template <int CW>
-__device__ __forceinline__ Chunk chunk_of(const AutocovBlock &a)
-{
-    Chunk k;
-    const int64_t b = (int64_t)blockIdx.x % a.n_chunks, rest = (int64_t)blockIdx.x / a.n_chunks;
-    const int64_t split = rest / a.d;
-    k.j = (int32_t)(rest % a.d);
-    k.r0 = a.n_rows * split / a.rsplit;
-    k.r1 = a.n_rows * (split + 1) / a.rsplit;
-    if (a.tpw > 0) {
-        k.t0 = b * a.tpw;
-        const int64_t left = a.n_targets - k.t0;
-        k.nt = (int32_t)(left < a.tpw ? left : a.tpw);
-        k.c0 = k.t0 * a.m;
-        k.m_loc = (int32_t)a.m;
-        k.nc = k.nt * k.m_loc;
-    } else {
-        k.t0 = b / a.cpt;
-        const int64_t first = (b % a.cpt) * CW, left = a.m - first;
-        k.c0 = k.t0 * a.m + first;
-        k.nc = (int32_t)(left < CW ? left : CW);
-        k.nt = 1;
-        k.m_loc = k.nc;
-    }
-    return k;
-}
-
-struct Lane {
-    int32_t wave, lc, lt;  // wavefront of the workgroup, chain within the chunk, target within the chunk
-    uint32_t same;         // bit s: the lane 2^s further on belongs to the same target
-    bool valid, head;
-};
-
-template <int CW>
-__device__ __forceinline__ Lane lane_of(const Chunk &k)
-{
-    constexpr int WPP = CW / 64;
-    Lane l;
-    const int lane = threadIdx.x % 64;
-    l.wave = threadIdx.x / 64;
-    l.lc = (l.wave % WPP) * 64 + lane;
-    l.valid = l.lc < k.nc;
-    l.lt = l.valid ? l.lc / k.m_loc : -1 - lane;  // (lanes without a chain: a segment each, never merged)
-    l.same = 0;
-    for (int s = 0; s < 6; ++s) {
-        const int other = __shfl_down(l.lt, 1 << s);
-        if (lane + (1 << s) < 64 && other == l.lt) l.same |= 1u << s;
-    }
-    const int prev = __shfl_up(l.lt, 1);
-    l.head = l.valid && (lane == 0 || prev != l.lt);
-    return l;
-}
-
-__device__ __forceinline__ double segmented_sum(double v, uint32_t same)
-{
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const double other = __shfl_down(v, 1 << s);
-        if (same & (1u << s)) v += other;
-    }
-    return v;
-}
 
 // (C, P, Q) of one lag per lane -> per target: steps 2 and 3 of the summation order.  The thread l.lc < k.nt of a group of
-// wavefronts is left with the sums of target l.lc of the chunk in c, p, q (the lane's own sums have gone into them).
-// lds: 3 x 1024 doubles.  Every thread of the workgroup calls it.
+// wavefronts is left with the sums of target l.lc of the chunk in c, p, q.  lds: 3 x 1024 doubles.
 template <int CW>
 __device__ __forceinline__ void fold3(const Chunk &k, const Lane &l, double &c, double &p, double &q, double *lds)
 {
-    constexpr int WPP = CW / 64;
-    c = segmented_sum(c, l.same);
-    p = segmented_sum(p, l.same);
-    q = segmented_sum(q, l.same);
-    if (l.head) {
-        lds[l.wave * CW + l.lt] = c;
-        lds[1024 + l.wave * CW + l.lt] = p;
-        lds[2048 + l.wave * CW + l.lt] = q;
-    }
-    __syncthreads();
-    if (l.lc < k.nt) {  // one thread per (group of wavefronts, target)
-        const int lt = l.lc, w0 = (l.wave / WPP) * WPP;
-        const int lo = (lt * k.m_loc) / 64, hi = ((lt + 1) * k.m_loc - 1) / 64;
-        c = lds[(w0 + lo) * CW + lt];
-        p = lds[1024 + (w0 + lo) * CW + lt];
-        q = lds[2048 + (w0 + lo) * CW + lt];
-        for (int w = lo + 1; w <= hi; ++w) {
-            c += lds[(w0 + w) * CW + lt];
-            p += lds[1024 + (w0 + w) * CW + lt];
-            q += lds[2048 + (w0 + w) * CW + lt];
-        }
-    }
+    double s[3] = {c, p, q};
+    fold<CW, 3>(k, l, s, lds, CW, 1024);
+    c = s[0];
+    p = s[1];
+    q = s[2];
     __syncthreads();
 }
 
@@ -159,8 +61,7 @@ template <int N>
 __device__ __forceinline__ void put_lags(const AutocovBlock &a, const Chunk &k, int lt, int lag0, double (&c)[N], double (&p)[N],
                                          double (&q)[N])
 {
-    double *row = a.ws ? a.ws + ((size_t)blockIdx.x * (a.tpw > 0 ? a.tpw : 1) + lt) * a.na
-                       : a.acc + ((size_t)(k.t0 + lt) * a.d + k.j) * a.na;
+    double *row = a.ws ? partials_of(a.cut, a.ws, lt, a.na) : a.acc + ((size_t)(k.t0 + lt) * a.cut.series + k.j) * a.na;
     if (!a.ws) {
 #pragma unroll
         for (int i = 0; i < N; ++i) {
@@ -248,7 +149,7 @@ __global__ void __launch_bounds__(kBlock) autocov_kernel(const AutocovBlock a)
     constexpr int CW = kBlock / SPLIT;
     constexpr int kLds = LC * kBlock > 3072 ? LC * kBlock : 3072;  // a lane's LC partial P, then fold3's 3 x 1024
     __shared__ double lds[kLds];
-    const Chunk k = chunk_of<CW>(a);
+    const Chunk k = chunk_of<CW, true>(a.cut);
     const Lane l = lane_of<CW>(k);
     const int g0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / CW) * LC);  // uniform in a wavefront
     double *park = lds + threadIdx.x;
@@ -282,21 +183,8 @@ __global__ void __launch_bounds__(kBlock) autocov_kernel(const AutocovBlock a)
     }
 }
 
-// Step 4 with a workspace: one thread per (target, series, sum) adds the target's partials in (row split, chunk) order.
-__global__ void __launch_bounds__(kBlock) autocov_fold_kernel(const AutocovBlock a)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n_targets * a.d * a.na) return;
-    const int64_t t = i / ((int64_t)a.d * a.na), j = i / a.na % a.d;
-    const int ai = (int)(i % a.na);
-    const int64_t stride = a.tpw > 0 ? a.tpw : 1;
-    const int64_t b0 = a.tpw > 0 ? t / a.tpw : t * a.cpt, lt = a.tpw > 0 ? t % a.tpw : 0;
-    const int64_t nb = a.tpw > 0 ? 1 : a.cpt;
-    double s = 0.0;
-    for (int64_t sp = 0; sp < a.rsplit; ++sp)
-        for (int64_t b = b0; b < b0 + nb; ++b) s += a.ws[(size_t)((((sp * a.d + j) * a.n_chunks + b) * stride + lt) * a.na + ai)];
-    a.acc[i] += s;
-}
+// Step 4 with a workspace.
+__global__ void __launch_bounds__(kBlock) autocov_fold_kernel(const TargetFold f) { fold_partials<false>(f); }
 
 }  // namespace
 
@@ -320,44 +208,16 @@ int launch_target_autocov(const double *ring, int64_t ring_rows, int64_t first_r
     a.sj = n_chains;
     a.ring_rows = ring_rows;
     a.first_row = first_row;
-    a.n_rows = n_rows;
     a.n_hist = n_hist;
-    a.n = n_chains;
-    a.m = m;
-    a.n_targets = n_chains / m;
-    a.d = d;
     a.n_lags = n_lags;
     a.na = (int32_t)autocov_sums(n_lags);
     a.acc = acc;
-    if (m <= cw) {
-        a.tpw = (int32_t)(cw / m);
-        a.n_chunks = ceil_div(a.n_targets, a.tpw);
-    } else {
-        a.cpt = (int32_t)ceil_div(m, cw);
-        a.n_chunks = a.n_targets * a.cpt;
-    }
-    a.rsplit = 1;
-    if (a.n_chunks * d < kWantGrid) {
-        const int64_t most = n_rows / kMinSplitRows, want = ceil_div(kWantGrid, a.n_chunks * d);
-        a.rsplit = (int32_t)(most < 1 ? 1 : (want < most ? want : most));
-    }
-    if (ceil_div(m, cw) > 0x7FFFFFFFll || a.n_chunks * d * a.rsplit > 0x7FFFFFFFll ||
-        a.n_targets * d * a.na > 0x7FFFFFFFll * kBlock) {
-        set_error("gsss_target_autocov: %lld chains of %lld per target exceed the grid", (long long)n_chains, (long long)m);
-        return GSSS_E_UNSUPPORTED;
-    }
-    // A workspace only where a target has more than one partial; taken and freed in stream order, like gsss_target_moments'.
-    void *ws = nullptr;
-    if (a.rsplit > 1 || a.tpw == 0) {
-        const size_t n_ws = (size_t)a.rsplit * d * a.n_chunks * (a.tpw > 0 ? a.tpw : 1) * a.na;
-        GSSS_HIP_TRY(hipMallocAsync(&ws, n_ws * sizeof(double), st));
-        a.ws = static_cast<double *>(ws);
-    }
-    int rc = launch_kernel("autocov", kern, a.n_chunks * d * a.rsplit, 0, st, nullptr, a);
-    if (rc == GSSS_OK && ws)
-        rc = launch_kernel("autocov fold", autocov_fold_kernel, ceil_div(a.n_targets * d * a.na, kBlock), 0, st, nullptr, a);
-    if (ws) (void)hipFreeAsync(ws, st);
-    return rc;
+    if (int rc = make_cut("gsss_target_autocov", n_chains, m, cw, cw, n_rows, kMinSplitRows, d, a.na, a.cut)) return rc;
+    const TargetFold f{a.cut, nullptr, acc, a.na, 0, a.na};
+    return launch_walk_and_fold("autocov fold", autocov_fold_kernel, f, 0, st, [&](double *ws, double *) {
+        a.ws = ws;
+        return launch_kernel("autocov", kern, a.cut.n_chunks * d * a.cut.rsplit, 0, st, nullptr, a);
+    });
 }
 
 }  // namespace gsss

@@ -1540,6 +1540,24 @@ int64_t gsss_moments_rows(int32_t d, int32_t flags)
     return 1 + moments_sums(d, diag);
 }
 
+// The checks that the per-target statistics share.  entry: the entry point's name, for the message.
+static int check_chains_per_target(const char *entry, int64_t n_chains, int64_t chains_per_target)
+{
+    if (chains_per_target >= 1 && n_chains >= 0 && n_chains % chains_per_target == 0) return GSSS_OK;
+    set_error("%s: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", entry, (long long)n_chains,
+              (long long)chains_per_target);
+    return GSSS_E_INVALID;
+}
+
+static int check_ring(const char *entry, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist)
+{
+    if (ring_rows >= 0 && first_row >= 0 && n_rows >= 0 && n_hist >= 0 && n_rows <= ring_rows && first_row <= ring_rows - n_rows)
+        return GSSS_OK;
+    set_error("%s: the rows %lld .. + %lld do not lie in a ring of %lld rows", entry, (long long)first_row, (long long)n_rows,
+              (long long)ring_rows);
+    return GSSS_E_INVALID;
+}
+
 int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_chains, int32_t d, int64_t samples_chain_rows,
                         int64_t chains_per_target, int32_t flags, double *acc_dev, double *chain_sum_dev, int device, void *stream)
 {
@@ -1547,11 +1565,7 @@ int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_cha
         set_error("gsss_target_moments: need d >= 2 and known flags (d = %d, flags = %d)", d, flags);
         return GSSS_E_INVALID;
     }
-    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
-        set_error("gsss_target_moments: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
-                  (long long)chains_per_target);
-        return GSSS_E_INVALID;
-    }
+    if (int rc = check_chains_per_target("gsss_target_moments", n_chains, chains_per_target)) return rc;
     if (n_rows < 0 || samples_chain_rows < 0 || (samples_chain_rows > 0 && samples_chain_rows < n_rows)) {
         set_error("gsss_target_moments: need n_rows >= 0 and samples_chain_rows 0 or >= n_rows (%lld rows, %lld per chain)",
                   (long long)n_rows, (long long)samples_chain_rows);
@@ -1577,11 +1591,7 @@ int gsss_target_moments(const double *samples_dev, int64_t n_rows, int64_t n_cha
 int gsss_scalar_moments(const double *values_dev, int64_t n_rows, int64_t n_chains, int64_t chains_per_target, double *acc_dev,
                         double *chain_sum_dev, int device, void *stream)
 {
-    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
-        set_error("gsss_scalar_moments: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
-                  (long long)chains_per_target);
-        return GSSS_E_INVALID;
-    }
+    if (int rc = check_chains_per_target("gsss_scalar_moments", n_chains, chains_per_target)) return rc;
     if (n_rows < 0) {
         set_error("gsss_scalar_moments: need n_rows >= 0 (%lld)", (long long)n_rows);
         return GSSS_E_INVALID;
@@ -1612,16 +1622,8 @@ int gsss_target_autocov(const double *ring_dev, int64_t ring_rows, int64_t first
         set_error("gsss_target_autocov: need d >= 1 and n_lags >= 1 (d = %d, n_lags = %d)", d, n_lags);
         return GSSS_E_INVALID;
     }
-    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
-        set_error("gsss_target_autocov: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
-                  (long long)chains_per_target);
-        return GSSS_E_INVALID;
-    }
-    if (ring_rows < 0 || first_row < 0 || n_rows < 0 || n_hist < 0 || n_rows > ring_rows || first_row > ring_rows - n_rows) {
-        set_error("gsss_target_autocov: the rows %lld .. + %lld do not lie in a ring of %lld rows", (long long)first_row,
-                  (long long)n_rows, (long long)ring_rows);
-        return GSSS_E_INVALID;
-    }
+    if (int rc = check_chains_per_target("gsss_target_autocov", n_chains, chains_per_target)) return rc;
+    if (int rc = check_ring("gsss_target_autocov", ring_rows, first_row, n_rows, n_hist)) return rc;
     if (n_hist > n_lags || n_hist > ring_rows - n_rows) {
         set_error("gsss_target_autocov: n_hist (%lld) exceeds n_lags (%d) or the ring's rows outside the block (%lld)",
                   (long long)n_hist, n_lags, (long long)(ring_rows - n_rows));
@@ -1658,16 +1660,8 @@ int gsss_target_mixing(const double *ring_dev, int64_t ring_rows, int64_t first_
                   flags);
         return GSSS_E_INVALID;
     }
-    if (chains_per_target < 1 || n_chains < 0 || n_chains % chains_per_target != 0) {
-        set_error("gsss_target_mixing: n_chains (%lld) must be a multiple of chains_per_target (%lld) >= 1", (long long)n_chains,
-                  (long long)chains_per_target);
-        return GSSS_E_INVALID;
-    }
-    if (ring_rows < 0 || first_row < 0 || n_rows < 0 || n_hist < 0 || n_rows > ring_rows || first_row > ring_rows - n_rows) {
-        set_error("gsss_target_mixing: the rows %lld .. + %lld do not lie in a ring of %lld rows", (long long)first_row,
-                  (long long)n_rows, (long long)ring_rows);
-        return GSSS_E_INVALID;
-    }
+    if (int rc = check_chains_per_target("gsss_target_mixing", n_chains, chains_per_target)) return rc;
+    if (int rc = check_ring("gsss_target_mixing", ring_rows, first_row, n_rows, n_hist)) return rc;
     if (n_hist > 1 || n_hist > ring_rows - n_rows) {
         set_error("gsss_target_mixing: n_hist (%lld) exceeds the one row of history or the ring's rows outside the block (%lld)",
                   (long long)n_hist, (long long)(ring_rows - n_rows));

@@ -7,36 +7,23 @@
 // (component-major input: for one (row, component) a wavefront reads 64 consecutive doubles).  Builds with a compile-time
 // d = 2 .. 16 keep x_{r-1}, its sign and its mode in the lane's registers, h_t as well; the one build with a run-time d keeps the
 // sign and the mode and reads row r - 1 a second time (the second read meets the first in the cache, as the SPLIT groups' reads
-// of gsss_moments.hip do).  Chunks of chains are cut at target boundaries as gsss_moments.hip cuts them: with m <= 256 a
-// workgroup takes whole targets -- as many as 256 lanes AND the LDS budget allow --, otherwise a target takes ceil(m / 256)
-// workgroups.
+// of gsss_moments.hip do).  The cut of the chains at target boundaries and the split of the rows over workgroups are
+// gsss_target_fold.h's, with CW = 256, one series and the targets of a workgroup capped by the LDS budget as well.
 //
 // LDS (dynamic, kMixingLdsBudget at most), per target of the workgroup: its counters (64-bit), its directions [1 + K][d] at an
 // odd stride in doubles (lanes of a wavefront that spans several targets read different banks; every lane has its own base) and
 // eight doubles for step 3 below.  Where one target's share exceeds the budget (large d) the directions stay in global memory.
 //
-// Summation order of the two floating-point sums (fixed by the arguments alone, no floating-point atomics: a call's result is
-// the same bits every time).
-//   1. a lane adds its chain's pairs in row order;
-//   2. the lanes of a wavefront are combined by a SEGMENTED shuffle reduction (offsets 1, 2, .. 32; a lane adds its neighbour
-//      only if that neighbour belongs to the same target), which leaves a target's sum in the first of its lanes;
-//   3. the wavefronts a target spans are added in wavefront order through LDS by one thread per target;
-//   4. where a target has a single partial (m <= 256 and the rows are not split over workgroups) that thread adds it to step;
-//      otherwise the partials go to a workspace and a second kernel adds them per target in (row split, chunk) order.
+// Summation order of the two floating-point sums: gsss_target_fold.h's steps 1 - 4 (a lane adds its chain's PAIRS in row order).
 // The counters are integers: a lane adds to its target's counters in LDS with integer atomics, the workgroup adds what it
 // counted to count[] with integer atomics on global memory -- the same result in any order.
-// The rows are split over workgroups only when the chains alone give fewer than kWantGrid workgroups; a workgroup that starts
-// inside the block takes x_{r-1} from the block's earlier row.  A pair (r, r - 1) counts where row r is.
-//
-// Chunk, Lane and segmented_sum are those of gsss_moments.hip and gsss_autocov.hip, kept local to this unit: each of the three
-// units cuts its grid its own way (series, lag groups), and their kernels stay instruction-identical only if left alone.
+// A workgroup that starts inside the block takes x_{r-1} from the block's earlier row.  A pair (r, r - 1) counts where row r is.
 #include "gsss_mixing.h"
-#include "gsss_launch.h"
+#include "gsss_target_fold.h"
 
 namespace gsss {
 namespace {
 
-constexpr int kWantGrid = 1024;  // workgroups below which the rows are split as well
 constexpr int kMinSplitRows = 32;
 constexpr size_t kMixingLdsBudget = 48 * 1024;  // directions, counters and fold scratch of a workgroup's targets
 constexpr int kFoldDoubles = 8;                 // per target: 2 sums x 4 wavefronts
@@ -46,83 +33,16 @@ using Counter = unsigned long long;
 struct MixingBlock {
     const double *x;
     int64_t sr, sj;  // doubles from row to row, component to component (the chains of a (row, component) are contiguous)
-    int64_t ring_rows, first_row, n_rows, n_hist;
-    int64_t n, m, n_targets, n_chunks;
-    int32_t d, n_modes, transitions, nc, rsplit;
-    int32_t tpw;     // targets a workgroup takes (m <= 256), else 0
-    int32_t cpt;     // workgroups a target takes (m > 256), else 0
+    TargetCut cut;   // CW = 256; tpw: also what the LDS budget allows
+    int64_t ring_rows, first_row, n_hist;
+    int32_t d, n_modes, transitions, nc;
     int32_t stride;  // doubles from target to target of the staged directions (odd); 0: they are read from global memory
     int64_t dn;      // doubles of a target's directions: (1 + n_modes) d
     const double *dirs;
     double *step;
     Counter *count;
-    double *ws;      // NULL: a target has one partial, added to step directly; else [rsplit][n_chunks][max(tpw, 1)][2]
+    double *ws;      // NULL: a target has one partial, added to step directly; else the workspace of partials_of
 };
-
-struct Chunk {
-    int64_t c0, t0;  // first chain, first target
-    int32_t nc, nt;  // chains, targets
-    int32_t m_loc;   // chains per target within the chunk
-    int64_t r0, r1;  // rows, relative to the block's first
-};
-
-__device__ __forceinline__ Chunk chunk_of(const MixingBlock &a)
-{
-    Chunk k;
-    const int64_t b = (int64_t)blockIdx.x % a.n_chunks, split = (int64_t)blockIdx.x / a.n_chunks;
-    k.r0 = a.n_rows * split / a.rsplit;
-    k.r1 = a.n_rows * (split + 1) / a.rsplit;
-    if (a.tpw > 0) {
-        k.t0 = b * a.tpw;
-        const int64_t left = a.n_targets - k.t0;
-        k.nt = (int32_t)(left < a.tpw ? left : a.tpw);
-        k.c0 = k.t0 * a.m;
-        k.m_loc = (int32_t)a.m;
-        k.nc = k.nt * k.m_loc;
-    } else {
-        k.t0 = b / a.cpt;
-        const int64_t first = (b % a.cpt) * kBlock, left = a.m - first;
-        k.c0 = k.t0 * a.m + first;
-        k.nc = (int32_t)(left < kBlock ? left : kBlock);
-        k.nt = 1;
-        k.m_loc = k.nc;
-    }
-    return k;
-}
-
-struct Lane {
-    int32_t wave, lc, lt;  // wavefront of the workgroup, chain within the chunk, target within the chunk
-    uint32_t same;         // bit s: the lane 2^s further on belongs to the same target
-    bool valid, head;
-};
-
-__device__ __forceinline__ Lane lane_of(const Chunk &k)
-{
-    Lane l;
-    const int lane = threadIdx.x % 64;
-    l.wave = threadIdx.x / 64;
-    l.lc = threadIdx.x;
-    l.valid = l.lc < k.nc;
-    l.lt = l.valid ? l.lc / k.m_loc : -1 - lane;  // (lanes without a chain: a segment each, never merged)
-    l.same = 0;
-    for (int s = 0; s < 6; ++s) {
-        const int other = __shfl_down(l.lt, 1 << s);
-        if (lane + (1 << s) < 64 && other == l.lt) l.same |= 1u << s;
-    }
-    const int prev = __shfl_up(l.lt, 1);
-    l.head = l.valid && (lane == 0 || prev != l.lt);
-    return l;
-}
-
-__device__ __forceinline__ double segmented_sum(double v, uint32_t same)
-{
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const double other = __shfl_down(v, 1 << s);
-        if (same & (1u << s)) v += other;
-    }
-    return v;
-}
 
 // Row q of the block (relative to its first; q = -1: the history row, round the ring's end) for the workgroup's first chain.
 __device__ __forceinline__ const double *row_at(const MixingBlock &a, const double *p, int64_t q)
@@ -250,12 +170,12 @@ template <int D>
 __global__ void __launch_bounds__(kBlock) mixing_kernel(const MixingBlock a)
 {
     extern __shared__ double lds[];
-    const Chunk k = chunk_of(a);
-    const Lane l = lane_of(k);
-    const int nt_max = a.tpw > 0 ? a.tpw : 1;
+    const Chunk k = chunk_of<kBlock, false>(a.cut);
+    const Lane l = lane_of<kBlock>(k);
+    const int nt_max = chunk_targets(a.cut);
     Counter *cnt = reinterpret_cast<Counter *>(lds);  // [nt_max][nc]
-    double *fold = lds + (size_t)nt_max * a.nc;       // [2][4][nt_max]
-    double *dirs = fold + (size_t)nt_max * kFoldDoubles;  // [nt_max][stride]
+    double *sums = lds + (size_t)nt_max * a.nc;       // [2][4][nt_max]
+    double *dirs = sums + (size_t)nt_max * kFoldDoubles;  // [nt_max][stride]
     for (int i = threadIdx.x; i < k.nt * a.nc; i += kBlock) cnt[i] = 0;
     if (a.stride > 0) {
         const double *src = a.dirs + (size_t)k.t0 * a.dn;
@@ -284,28 +204,17 @@ __global__ void __launch_bounds__(kBlock) mixing_kernel(const MixingBlock a)
         atomicAdd(mine + 2, w.hops);
     }
     // steps 2 - 4 of the summation order
-    const double s1 = segmented_sum(w.s1, l.same), s2 = segmented_sum(w.s2, l.same);
-    if (l.head) {
-        fold[l.wave * nt_max + l.lt] = s1;
-        fold[(4 + l.wave) * nt_max + l.lt] = s2;
-    }
-    __syncthreads();
+    double t[2] = {w.s1, w.s2};
+    fold<kBlock, 2>(k, l, t, sums, nt_max, 4 * nt_max);
     if (l.lc < k.nt) {  // one thread per target
-        const int lt = l.lc;
-        const int lo = (lt * k.m_loc) / 64, hi = ((lt + 1) * k.m_loc - 1) / 64;
-        double t1 = fold[lo * nt_max + lt], t2 = fold[(4 + lo) * nt_max + lt];
-        for (int wv = lo + 1; wv <= hi; ++wv) {
-            t1 += fold[wv * nt_max + lt];
-            t2 += fold[(4 + wv) * nt_max + lt];
-        }
         if (a.ws) {
-            double *o = a.ws + ((size_t)blockIdx.x * nt_max + lt) * 2;
-            o[0] = t1;
-            o[1] = t2;
+            double *o = partials_of(a.cut, a.ws, l.lc, 2);
+            o[0] = t[0];
+            o[1] = t[1];
         } else {
-            double *o = a.step + (size_t)(k.t0 + lt) * 2;
-            o[0] += t1;
-            o[1] += t2;
+            double *o = a.step + (size_t)(k.t0 + l.lc) * 2;
+            o[0] += t[0];
+            o[1] += t[1];
         }
     }
     Counter *out = a.count + (size_t)k.t0 * a.nc;
@@ -313,21 +222,8 @@ __global__ void __launch_bounds__(kBlock) mixing_kernel(const MixingBlock a)
         if (cnt[i] != 0) atomicAdd(out + i, cnt[i]);
 }
 
-// Step 4 with a workspace: one thread per (target, sum) adds the target's partials in (row split, chunk) order.
-__global__ void __launch_bounds__(kBlock) mixing_fold_kernel(const MixingBlock a)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n_targets * 2) return;
-    const int64_t t = i / 2;
-    const int ai = (int)(i % 2);
-    const int64_t stride = a.tpw > 0 ? a.tpw : 1;
-    const int64_t b0 = a.tpw > 0 ? t / a.tpw : t * a.cpt, lt = a.tpw > 0 ? t % a.tpw : 0;
-    const int64_t nb = a.tpw > 0 ? 1 : a.cpt;
-    double s = 0.0;
-    for (int64_t sp = 0; sp < a.rsplit; ++sp)
-        for (int64_t b = b0; b < b0 + nb; ++b) s += a.ws[(size_t)(((sp * a.n_chunks + b) * stride + lt) * 2 + ai)];
-    a.step[i] += s;
-}
+// Step 4 with a workspace.
+__global__ void __launch_bounds__(kBlock) mixing_fold_kernel(const TargetFold f) { fold_partials<false>(f); }
 
 using MixingKernel = void (*)(const MixingBlock);
 
@@ -365,11 +261,7 @@ int launch_target_mixing(const double *ring, int64_t ring_rows, int64_t first_ro
     a.sj = n_chains;
     a.ring_rows = ring_rows;
     a.first_row = first_row;
-    a.n_rows = n_rows;
     a.n_hist = n_hist;
-    a.n = n_chains;
-    a.m = m;
-    a.n_targets = n_chains / m;
     a.d = d;
     a.n_modes = n_modes;
     a.transitions = transitions && n_modes > 0 ? 1 : 0;
@@ -386,35 +278,15 @@ int launch_target_mixing(const double *ring, int64_t ring_rows, int64_t first_ro
         a.stride = 0;
         per_target = bare;
     }
-    if (m <= kBlock) {
-        const int64_t by_lanes = kBlock / m, by_lds = (int64_t)(kMixingLdsBudget / per_target);
-        a.tpw = (int32_t)(by_lanes < by_lds ? by_lanes : by_lds);
-        a.n_chunks = ceil_div(a.n_targets, a.tpw);
-    } else {
-        a.cpt = (int32_t)ceil_div(m, kBlock);
-        a.n_chunks = a.n_targets * a.cpt;
-    }
-    a.rsplit = 1;
-    if (a.n_chunks < kWantGrid) {
-        const int64_t most = n_rows / kMinSplitRows, want = ceil_div(kWantGrid, a.n_chunks);
-        a.rsplit = (int32_t)(most < 1 ? 1 : (want < most ? want : most));
-    }
-    if (ceil_div(m, kBlock) > 0x7FFFFFFFll || a.n_chunks * a.rsplit > 0x7FFFFFFFll || a.n_targets * 2 > 0x7FFFFFFFll * kBlock) {
-        set_error("gsss_target_mixing: %lld chains of %lld per target exceed the grid", (long long)n_chains, (long long)m);
-        return GSSS_E_UNSUPPORTED;
-    }
-    const size_t lds = per_target * (a.tpw > 0 ? a.tpw : 1);
-    // A workspace only where a target has more than one partial; taken and freed in stream order, like gsss_target_moments'.
-    void *ws = nullptr;
-    if (a.rsplit > 1 || a.tpw == 0) {
-        const size_t n_ws = (size_t)a.rsplit * a.n_chunks * (a.tpw > 0 ? a.tpw : 1) * 2;
-        GSSS_HIP_TRY(hipMallocAsync(&ws, n_ws * sizeof(double), st));
-        a.ws = static_cast<double *>(ws);
-    }
-    int rc = launch_kernel("mixing", kern, a.n_chunks * a.rsplit, lds, st, nullptr, a);
-    if (rc == GSSS_OK && ws) rc = launch_kernel("mixing fold", mixing_fold_kernel, ceil_div(a.n_targets * 2, kBlock), 0, st, nullptr, a);
-    if (ws) (void)hipFreeAsync(ws, st);
-    return rc;
+    if (int rc = make_cut("gsss_target_mixing", n_chains, m, kBlock, (int64_t)(kMixingLdsBudget / per_target), n_rows, kMinSplitRows,
+                          1, 2, a.cut))
+        return rc;
+    const size_t lds = per_target * chunk_targets(a.cut);
+    const TargetFold f{a.cut, nullptr, step, 2, 0, 2};
+    return launch_walk_and_fold("mixing fold", mixing_fold_kernel, f, 0, st, [&](double *ws, double *) {
+        a.ws = ws;
+        return launch_kernel("mixing", kern, a.cut.n_chunks * a.cut.rsplit, lds, st, nullptr, a);
+    });
 }
 
 }  // namespace gsss

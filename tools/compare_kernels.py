@@ -7,8 +7,10 @@ build.sources().  Reported per unit and for the union of the kernels over all un
 union a name counts as different if any of its bodies differs).  Normalised: the literal that follows s_getpc_b64 (the
 pc-relative address of a table) and the padding behind a function depend on where the object was laid out, not on the kernel.  Up to 16 compilations run in
 parallel (--jobs).  A body that differs is also compared by its count per opcode with s_nop and s_waitcnt left out: equal
-counts mean the same work in another order ("scheduling only"); the exit status is 0 if no kernel differs by more than that
-(and, with --resources, in no figure), else 1.
+counts mean the same work in another order ("scheduling only"); failing that, equal counts over every opcode that ends in _f64,
+every opcode that begins with global_, flat_ or buffer_, and s_barrier mean "the same arithmetic and memory work" around other
+integer and scalar bookkeeping.  The exit status is 0 if no kernel differs by more than its schedule -- with --same-work-ok, by
+more than that bookkeeping -- (and, with --resources, in no figure), else 1.
     python tools/compare_kernels.py --resources <other tree> [units ...]
 compares each kernel's resource figures as well, in the code object's metadata: VGPRs (all of them; AGPRs are among them and
 also given alone), SGPRs, spills, scratch and static LDS bytes, and the wavefronts per SIMD that the registers allow (512 / VGPRs
@@ -47,6 +49,17 @@ def scheduling_only(x, y):
     return count(x) == count(y)
 
 
+def same_work(x, y):
+    def count(body):
+        ops = (i.split()[0] for i in body)
+        return collections.Counter(o for o in ops if o.endswith("_f64") or o.startswith(("global_", "flat_", "buffer_")) or o == "s_barrier")
+    return count(x) == count(y)
+
+
+# how far a differing body is from the other one
+VERDICTS = ("scheduling only", "same arithmetic and memory work", "OTHER OPCODE COUNTS")
+
+
 def functions(tree, unit, tmp, tag, want_resources=False):
     co, elf = os.path.join(tmp, f"{tag}.co"), os.path.join(tmp, f"{tag}.elf")
     subprocess.run([build.hipcc(), *build.CXXFLAGS, *build.source_flags(unit), "--cuda-device-only", "-c",
@@ -70,33 +83,35 @@ def functions(tree, unit, tmp, tag, want_resources=False):
     return d, (resources(elf) if want_resources else {})
 
 
-def report(label, a, b, sched=None):
+def report(label, a, b, sched=None, allow=0):
     """a, b: {kernel: body} there and here (resources: its figures; the union: the set of its bodies or figures).  `sched`:
-    {kernel: all its differing bodies were scheduling only}, filled from the units' bodies and read for the union.  Prints one
-    line and the offenders; returns how many are missing, new or differ by more than their schedule."""
+    {kernel: the worst verdict (index into VERDICTS) of its differing bodies}, filled from the units' bodies and read for the
+    union.  Prints one line and the offenders; returns how many are missing, new or differ by a verdict beyond `allow`."""
     same = [k for k in a if a[k] == b.get(k)]
     diff = [k for k in a if k in b and a[k] != b[k]]
     gone = [k for k in a if k not in b]
     new = [k for k in b if k not in a]
     print(f"{label}: {len(a)} kernels there, {len(b)} here; identical: {len(same)}, different: {len(diff)}, "
           f"missing here: {len(gone)}, new here: {len(new)}")
-    worse = 0
+    worse, by_verdict = 0, [0] * len(VERDICTS)
     for k in diff + gone + new:
-        note, only = "", False
+        note, verdict = "", len(VERDICTS) - 1
         if k in diff and isinstance(a[k], list):  # one unit's bodies
-            only = scheduling_only(a[k], b[k])
+            verdict = 0 if scheduling_only(a[k], b[k]) else (1 if same_work(a[k], b[k]) else 2)
             if sched is not None:
-                sched[k] = only and sched.get(k, True)
-            note = f"  [{len(a[k])} -> {len(b[k])} instructions, " + ("scheduling only]" if only else "OTHER OPCODE COUNTS]")
+                sched[k] = max(verdict, sched.get(k, 0))
+            note = f"  [{len(a[k])} -> {len(b[k])} instructions, {VERDICTS[verdict]}]"
         elif k in diff and isinstance(a[k], tuple):  # one unit's resource figures
             note = f"  {a[k]} -> {b[k]}"
         elif k in diff and sched is not None and k in sched:  # the union of the bodies
-            only = sched[k]
-            note = "  [scheduling only]" if only else "  [OTHER OPCODE COUNTS]"
-        worse += not only
+            verdict = sched[k]
+            note = f"  [{VERDICTS[verdict]}]"
+        worse += verdict > allow
+        by_verdict[verdict] += k in diff
         print("   ", "different" if k in diff else "missing  " if k in gone else "new      ", k + note)
     if diff:
-        print(f"    of the different: scheduling only {len(diff) + len(gone) + len(new) - worse}, more than that {worse - len(gone) - len(new)}")
+        print(f"    of the different: scheduling only {by_verdict[0]}, same arithmetic and memory work {by_verdict[1]}, "
+              f"more than that {by_verdict[2]}")
     return worse
 
 
@@ -105,6 +120,8 @@ def main():
     ap.add_argument("other", help="the other source tree")
     ap.add_argument("units", nargs="*", help="translation units (default: every unit of the build)")
     ap.add_argument("--resources", action="store_true", help="also compare resource figures " + str(RESOURCE_KEYS + ("waves/SIMD",)))
+    ap.add_argument("--same-work-ok", action="store_true",
+                    help='the exit status treats "same arithmetic and memory work" like "scheduling only"')
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 1))
     a = ap.parse_args()
     units = a.units or build.sources()
@@ -119,7 +136,7 @@ def main():
             return one
         there = list(ex.map(side(a.other, "other"), units))
         here = list(ex.map(side(HERE, "this"), units))
-    bad = 0
+    bad, allow = 0, 1 if a.same_work_ok else 0
     for what in range(2 if a.resources else 1):  # the bodies, then the resource figures
         union_there, union_here, sched = {}, {}, ({} if what == 0 else None)
         for union, per_unit in ((union_there, there), (union_here, here)):
@@ -127,9 +144,9 @@ def main():
                 for k, body in fns[what].items():  # one name, several bodies (weak copies in several units): all of them
                     union.setdefault(k, set()).add(tuple(body))
         for unit, x, y in zip(units, there, here):
-            report(unit + (" resources" if what else ""), x[what], y[what], sched)
-        bad += report("union of all units" + (" resources" if what else ""), union_there, union_here, sched)
-    # exit status: 0 if every kernel is identical or differs in its schedule only (and, with --resources, in no figure)
+            report(unit + (" resources" if what else ""), x[what], y[what], sched, allow)
+        bad += report("union of all units" + (" resources" if what else ""), union_there, union_here, sched, allow)
+    # exit status: 0 if every kernel is identical or differs by an allowed verdict only (and, with --resources, in no figure)
     sys.exit(1 if bad else 0)
 
 
