@@ -14,10 +14,13 @@ the GPU.  One scalar series gives the reference's scalar.
 import numpy as np
 import torch
 
+from . import _lib
+from .sphere import current_stream_ptr
+
 __all__ = ["acf", "acf_fft", "IAT", "n_eff", "distance", "hopping_frequency", "mode_occupancy", "mode_kl", "from_running",
            "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments",
            "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw", "target_autocov", "from_target_autocov",
-           "target_mixing", "from_target_mixing"]
+           "target_mixing", "from_target_mixing", "ring_plan"]
 
 
 def _t(x):
@@ -251,6 +254,27 @@ def ess_between_chains(chain_means, n, chain_vars):
             "rel_se": float(np.sqrt(2.0 / (m.numel() - 1))), "n": n_draws, "chains": int(m.numel())}
 
 
+def _accumulator(name, t, shape, like, of="x", dtype=torch.float64):
+    """The accumulator t, or zeros for None; ValueError unless it is contiguous, of this shape and dtype, on the device of `like`."""
+    if t is None:
+        return torch.zeros(shape, dtype=dtype, device=like.device)
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != like.device
+            or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {str(dtype)[6:]} tensor {tuple(shape)} on the device of {of}")
+    return t
+
+
+def _chains_per_target(chains_per_target, n):
+    m = int(chains_per_target)
+    if m < 1 or n % m:
+        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+    return m
+
+
+def _device_index(t):
+    return t.device.index if t.device.index is not None else torch.cuda.current_device()
+
+
 def _moments_form(d, second_moment):
     """(keep the full triangle?, accumulator rows per target) -- the rows of gsss_moments_rows."""
     full = d <= 16 if second_moment is None else bool(second_moment)
@@ -268,11 +292,8 @@ def target_moments(x, chains_per_target, *, chain_major=False, second_moment=Non
     draws, rows 1 .. d the sums of x_j, then the d (d + 1) / 2 sums of x_i x_j (i <= j, row-major; second_moment=None keeps them
     for d <= 16) or, with second_moment=False, the d sums of x_j^2.  `acc` continues an earlier accumulator (added to, returned);
     `chain_sum`, a (d, n) tensor, has every chain's sum of its R draws added to it."""
-    from . import _lib
-    from .sphere import current_stream_ptr
     if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64 or x.ndim != 3:
         raise ValueError("x must be a CUDA float64 tensor (R, d, n), or (n, R, d) with chain_major=True")
-    m = int(chains_per_target)
     if chain_major:
         n, R, d = (int(v) for v in x.shape)
         if n * R and not (x.stride(2) == 1 and x.stride(1) == d and x.stride(0) % d == 0 and x.stride(0) >= R * d):
@@ -282,21 +303,13 @@ def target_moments(x, chains_per_target, *, chain_major=False, second_moment=Non
         R, d, n = (int(v) for v in x.shape)
         x, chain_rows = x.contiguous(), 0
     full, rows = _moments_form(d, second_moment)
-    if m < 1 or n % m:
-        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
-    M = n // m
-    if acc is None:
-        acc = torch.zeros((M, rows), dtype=torch.float64, device=x.device)
-    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (M, rows) or acc.dtype != torch.float64 or acc.device != x.device
-          or not acc.is_contiguous()):
-        raise ValueError(f"acc must be a contiguous float64 tensor ({M}, {rows}) on the device of x")
-    if chain_sum is not None and (not isinstance(chain_sum, torch.Tensor) or tuple(chain_sum.shape) != (d, n)
-                                  or chain_sum.dtype != torch.float64 or chain_sum.device != x.device
-                                  or not chain_sum.is_contiguous()):
-        raise ValueError(f"chain_sum must be a contiguous float64 tensor ({d}, {n}) on the device of x")
+    m = _chains_per_target(chains_per_target, n)
+    acc = _accumulator("acc", acc, (n // m, rows), x)
+    if chain_sum is not None:
+        _accumulator("chain_sum", chain_sum, (d, n), x)
     if R == 0 or n == 0:
         return acc
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(x)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().gsss_target_moments(x.data_ptr(), R, n, d, chain_rows, m, 0 if full else _lib.MOMENTS_DIAG,
                                                    acc.data_ptr(), None if chain_sum is None else chain_sum.data_ptr(), dev,
@@ -378,8 +391,6 @@ def target_log_prob(batch, x, *, chain_major=False, target0=0):
     chain_major=True, (N, R, d) -- what `sample(..., as_tensor=True)` returns -- -> (N, R).  The block covers the targets
     target0 .. len(batch) - 1, each with the same number of chains: m = N / (len(batch) - target0), which must divide; chain c
     belongs to target target0 + c // m.  The values are the members' own `log_prob`, bit for bit."""
-    from . import _lib
-    from .sphere import current_stream_ptr
     if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64 or x.ndim != 3:
         raise ValueError("x must be a CUDA float64 tensor (R, d, N), or (N, R, d) with chain_major=True")
     N, R, d = (int(v) for v in (x.shape if chain_major else (x.shape[2], x.shape[0], x.shape[1])))
@@ -396,7 +407,7 @@ def target_log_prob(batch, x, *, chain_major=False, target0=0):
     out = torch.empty((N, R) if chain_major else (R, N), dtype=torch.float64, device=x.device)
     if R == 0:
         return out
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(x)
     tgt = batch._device_target(x.device, chains_per_target=m)
     with torch.cuda.device(dev):
         if chain_major and target0 == 0:   # (N, R, d) is row-major (M, m R, d): every member at its own rows
@@ -415,27 +426,17 @@ def scalar_moments(values, chains_per_target, *, acc=None, chain_sum=None):
     """`target_moments` for one scalar per draw (gsss_scalar_moments): values (R, N), a CUDA float64 tensor, target t owning the
     chains [t m, (t + 1) m).  Returns acc (M, 3): count, sum v, sum v^2 -- `acc` continues an earlier one; `chain_sum` (N,) has
     every chain's sum of its R values added to it.  The same kernels, the same fixed summation order."""
-    from . import _lib
-    from .sphere import current_stream_ptr
     if not isinstance(values, torch.Tensor) or not values.is_cuda or values.dtype != torch.float64 or values.ndim != 2:
         raise ValueError("values must be a CUDA float64 tensor (R, N)")
     values = values.contiguous()
     R, N = (int(v) for v in values.shape)
-    m = int(chains_per_target)
-    if m < 1 or N % m:
-        raise ValueError(f"the number of chains ({N}) must be a multiple of chains_per_target ({chains_per_target})")
-    if acc is None:
-        acc = torch.zeros((N // m, 3), dtype=torch.float64, device=values.device)
-    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (N // m, 3) or acc.dtype != torch.float64
-          or acc.device != values.device or not acc.is_contiguous()):
-        raise ValueError(f"acc must be a contiguous float64 tensor ({N // m}, 3) on the device of the values")
-    if chain_sum is not None and (not isinstance(chain_sum, torch.Tensor) or tuple(chain_sum.shape) != (N,)
-                                  or chain_sum.dtype != torch.float64 or chain_sum.device != values.device
-                                  or not chain_sum.is_contiguous()):
-        raise ValueError(f"chain_sum must be a contiguous float64 tensor ({N},) on the device of the values")
+    m = _chains_per_target(chains_per_target, N)
+    acc = _accumulator("acc", acc, (N // m, 3), values, of="the values")
+    if chain_sum is not None:
+        _accumulator("chain_sum", chain_sum, (N,), values, of="the values")
     if R == 0 or N == 0:
         return acc
-    dev = values.device.index if values.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(values)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().gsss_scalar_moments(values.data_ptr(), R, N, m, acc.data_ptr(),
                                                    None if chain_sum is None else chain_sum.data_ptr(), dev, current_stream_ptr(dev)))
@@ -491,9 +492,7 @@ def target_autocov(x, chains_per_target, lags, *, acc=None, hist=None):
     if x.ndim == 2:
         x = x[:, None, :]
     R, d, n = (int(v) for v in x.shape)
-    m, L = int(chains_per_target), int(lags)
-    if m < 1 or n % m:
-        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+    m, L = _chains_per_target(chains_per_target, n), int(lags)
     if not 1 <= L <= 64:
         raise ValueError(f"lags must be 1 .. 64 (got {lags})")
     M, h = n // m, 0
@@ -504,11 +503,7 @@ def target_autocov(x, chains_per_target, lags, *, acc=None, hist=None):
                 or hist.device != x.device or hist.shape[0] > L):
             raise ValueError(f"hist must be a float64 tensor of at most {L} rows shaped like the rows of x, on the device of x")
         h = int(hist.shape[0])
-    if acc is None:
-        acc = torch.zeros((M, d, L + 1, 3), dtype=torch.float64, device=x.device)
-    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (M, d, L + 1, 3) or acc.dtype != torch.float64
-          or acc.device != x.device or not acc.is_contiguous()):
-        raise ValueError(f"acc must be a contiguous float64 tensor ({M}, {d}, {L + 1}, 3) on the device of x")
+    acc = _accumulator("acc", acc, (M, d, L + 1, 3), x)
     if R == 0 or n == 0:
         return acc
     ring = torch.cat([x, hist]) if h else x.contiguous()     # the rows before row 0 of a ring are its last
@@ -518,10 +513,8 @@ def target_autocov(x, chains_per_target, lags, *, acc=None, hist=None):
 
 def _autocov_fold(ring, first_row, n_rows, n_hist, m, lags, acc):
     """gsss_target_autocov on the rows first_row .. + n_rows of a contiguous ring (rows, d, n)."""
-    from . import _lib
-    from .sphere import current_stream_ptr
     rows, d, n = (int(v) for v in ring.shape)
-    dev = ring.device.index if ring.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(ring)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().gsss_target_autocov(ring.data_ptr(), rows, first_row, n_rows, n_hist, n, d, m, lags, acc.data_ptr(),
                                                    dev, current_stream_ptr(dev)))
@@ -593,9 +586,7 @@ def target_mixing(x, chains_per_target, *, hop=None, modes=None, transitions=Fal
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.ndim != 3:
         raise ValueError("x must be a CUDA float64 tensor (R, d, n)")
     R, d, n = (int(v) for v in x.shape)
-    m = int(chains_per_target)
-    if m < 1 or n % m:
-        raise ValueError(f"the number of chains ({n}) must be a multiple of chains_per_target ({chains_per_target})")
+    m = _chains_per_target(chains_per_target, n)
     if d < 2:
         raise ValueError("a point on a sphere has two coordinates at least")
     M, h = n // m, 0
@@ -608,16 +599,8 @@ def target_mixing(x, chains_per_target, *, hop=None, modes=None, transitions=Fal
                 or hist.device != x.device or hist.shape[0] > 1):
             raise ValueError("hist must be a float64 tensor of at most one row shaped like the rows of x, on the device of x")
         h = int(hist.shape[0])
-    if step is None:
-        step = torch.zeros((M, 2), dtype=torch.float64, device=x.device)
-    elif (not isinstance(step, torch.Tensor) or tuple(step.shape) != (M, 2) or step.dtype != torch.float64 or step.device != x.device
-          or not step.is_contiguous()):
-        raise ValueError(f"step must be a contiguous float64 tensor ({M}, 2) on the device of x")
-    if counts is None:
-        counts = torch.zeros((M, rows), dtype=torch.int64, device=x.device)
-    elif (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (M, rows) or counts.dtype != torch.int64
-          or counts.device != x.device or not counts.is_contiguous()):
-        raise ValueError(f"counts must be a contiguous int64 tensor ({M}, {rows}) on the device of x")
+    step = _accumulator("step", step, (M, 2), x)
+    counts = _accumulator("counts", counts, (M, rows), x, dtype=torch.int64)
     if R == 0 or n == 0:
         return step, counts
     ring = torch.cat([x, hist]) if h else x.contiguous()     # the row before row 0 of a ring is its last
@@ -627,10 +610,8 @@ def target_mixing(x, chains_per_target, *, hop=None, modes=None, transitions=Fal
 
 def _mixing_fold(ring, first_row, n_rows, n_hist, m, dirs, n_modes, transitions, step, counts):
     """gsss_target_mixing on the rows first_row .. + n_rows of a contiguous ring (rows, d, n)."""
-    from . import _lib
-    from .sphere import current_stream_ptr
     rows, d, n = (int(v) for v in ring.shape)
-    dev = ring.device.index if ring.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(ring)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().gsss_target_mixing(ring.data_ptr(), rows, first_row, n_rows, n_hist, n, d, m, dirs.data_ptr(), n_modes,
                                                   _lib.MIXING_TRANSITIONS if transitions else 0, step.data_ptr(), counts.data_ptr(),
@@ -687,9 +668,7 @@ LADDER_SLOTS = 10  # doubles per pair-chain of gsss_batch_ladder
 def _ladder_fold(handle, lib, x, n_rows, n, target0, ladder, scratch, acc):
     """gsss_batch_ladder on the first n_rows rows of the contiguous block x (.., d, n) of the batch handle's members from
     target0 on; scratch holds 3 n_rows n doubles."""
-    from . import _lib
-    from .sphere import current_stream_ptr
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(x)
     with torch.cuda.device(dev):
         _lib.check(lib.gsss_batch_ladder(handle, x.data_ptr(), n_rows, n, target0, ladder, scratch.data_ptr(), acc.data_ptr(),
                                          current_stream_ptr(dev)))
@@ -720,12 +699,7 @@ def target_ladder(batch, x, ladder, *, chain_major=False, acc=None):
     if N < M or N % M:
         raise ValueError(f"the number of chains ({N}) must be a multiple of the batch's {M} targets, with at least one chain each")
     m = N // M
-    shape = (M // R, R - 1, m, LADDER_SLOTS)
-    if acc is None:
-        acc = torch.zeros(shape, dtype=torch.float64, device=x.device)
-    elif (not isinstance(acc, torch.Tensor) or tuple(acc.shape) != shape or acc.dtype != torch.float64 or acc.device != x.device
-          or not acc.is_contiguous()):
-        raise ValueError(f"acc must be a contiguous float64 tensor {shape} on the device of x")
+    acc = _accumulator("acc", acc, (M // R, R - 1, m, LADDER_SLOTS), x)
     if rows == 0:
         return acc
     tgt = batch._device_target(x.device, chains_per_target=m)
@@ -789,15 +763,38 @@ def from_target_ladder(acc, *, hot_log_z=None):
             "used": used, "skipped": skipped, "log_z": log_z}
 
 
+def ring_plan(rest, window, hist_rows, seen):
+    """How `Sampler.summarize` lays 1 + rest retained draws into its one reused buffer, in integers alone: windows of up to
+    `window` rows behind H = hist_rows rows of history, `seen` (<= H) of which an earlier call left.  -> (rows, draw0, windows, keep):
+    rows = H + window, the buffer's; draw0 = (row, 1, n_hist) of draw 0, or None where H = 0 and the state itself is folded as a
+    window of one; windows = [(first_row, n_rows, n_hist), ..] of the draws after it; keep: the rows that hold the last
+    min(H, draws so far) draws at the end, oldest first -- the next call's history.  Without history every window starts at row 0.
+    With it the buffer is a ring: the earlier call's rows lie at 0 .. seen - 1, draw 0 at row `seen`, the windows follow one behind
+    the other, each cut at the ring's end so that none wraps; the n_hist = min(H, draws so far) rows before a window, taken round
+    the ring's end, are the draws before it."""
+    H, rows = hist_rows, hist_rows + window
+    if not H:
+        return rows, None, [(0, min(window, rest - done), 0) for done in range(0, rest, window)], []
+    draw0, windows = (seen, 1, seen), []
+    pos, seen, done = seen + 1, seen + 1, 0
+    while done < rest:
+        pos %= rows
+        w = min(window, rest - done, rows - pos)
+        windows.append((pos, w, min(H, seen)))
+        pos, seen, done = pos + w, seen + w, done + w
+    return rows, draw0, windows, [(pos - min(H, seen) + i) % rows for i in range(min(H, seen))]
+
+
 class TargetMoments:
     """What `Sampler.summarize` returns: the per-target accumulators of a run (`acc` (M, rows), `chain_sum` (d, n), device
-    tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`.
+    tensors; see `target_moments`) and what they belong to.  stats() -> `from_target_moments`.  Everything a statistic of
+    `summarize` needs is here: `begin` allocates what it keeps, `check_continues` says why into= cannot take it up, `fold` adds one
+    window to it, `stats` reports it.
 
     With `summarize(lags=L)` also the lagged products of every coordinate: `lags` = L, `acov` (M, d, L + 1, 3) (see
     `target_autocov`) and `hist`, the last min(L, draws) retained rows (h, d, n), from which into= goes on; with log_prob=True
     `lp_acov` (M, 1, L + 1, 3) and `lp_hist` (h, 1, n) for the log-density series.  stats() then adds acf, iat, ess_within,
     iat_truncated (`from_target_autocov`) and lp_acf, lp_iat, lp_ess_within, lp_iat_truncated.
-
 
     With `summarize(log_prob=True)` also the log-density trace: `lp_acc` (M, 3) -- count, sum, sum of squares of log_prob over
     the target's draws --, `lp_chain_sum` (n,), and the best draw seen per target, `lp_best` (M,) and `x_best` (M, d): the maximum
@@ -827,9 +824,112 @@ class TargetMoments:
         self.mix_dirs, self.mix_transitions = None, False
         self.ladder, self.ladder_acc, self._ladder_hot, self._ladder_source = None, None, None, None
 
+    @classmethod
+    def begin(cls, n, d, chains_per_target, device, *, second_moment=None, log_prob=False, lags=None, mixing=None, ladder=None,
+              ladder_source=None):
+        """Zeroed accumulators of n chains in d dimensions on `device` and of the features asked for: log_prob, lags = L, mixing =
+        dict(hop, modes, weights, transitions), ladder = R with ladder_source = (batch, first ladder) for `ladder_hot_log_z`."""
+        m = int(chains_per_target)
+        M = n // m
+        full, rows = _moments_form(d, second_moment)
+
+        def zeros(*shape, dtype=torch.float64):
+            return torch.zeros(shape, dtype=dtype, device=device)
+        tm = cls(zeros(M, rows), zeros(d, n), d, m, full)
+        if log_prob:
+            tm.lp_acc, tm.lp_chain_sum, tm.x_best = zeros(M, 3), zeros(n), zeros(M, d)
+            tm.lp_best = torch.full((M,), float("-inf"), dtype=torch.float64, device=device)
+        if lags is not None:
+            tm.lags = int(lags)
+            tm.acov = zeros(M, d, tm.lags + 1, 3)
+            if log_prob:
+                tm.lp_acov = zeros(M, 1, tm.lags + 1, 3)
+        if mixing is not None:
+            tm.mix_dirs, tm.mix_modes = _mixing_dirs(mixing["hop"], mixing["modes"], M, d, device)
+            tm.mix_transitions = mixing["transitions"]
+            if mixing["weights"] is not None:
+                w = _t(mixing["weights"]).to(torch.float64)
+                w = w[None].expand(M, -1) if w.ndim == 1 else w
+                if tm.mix_modes == 0 or tuple(w.shape) != (M, tm.mix_modes):
+                    raise ValueError(f"weights must be (K,) or (M, K) = ({M}, {tm.mix_modes}), one per mode direction")
+                tm.mix_weights = w.contiguous().to(device)
+            tm.mix_step = zeros(M, 2)
+            tm.mix_counts = zeros(M, 3 + tm.mix_modes + (tm.mix_modes ** 2 if tm.mix_transitions else 0), dtype=torch.int64)
+        if ladder is not None:
+            tm.ladder, tm._ladder_source = ladder, ladder_source
+            tm.ladder_acc = zeros(M // ladder, ladder - 1, m, LADDER_SLOTS)
+        return tm
+
+    def check_continues(self, n, d, chains_per_target, *, second_moment=None, log_prob=False, lags=None, mixing=None, ladder=None):
+        """ValueError unless into= can go on with this call: the same chains and form, and no feature it was begun without."""
+        full, rows = _moments_form(d, self.second_moment if second_moment is None else second_moment)
+        M = n // chains_per_target
+        if (self.d != d or self.chains_per_target != chains_per_target or self.second_moment != full
+                or tuple(self.acc.shape) != (M, rows) or tuple(self.chain_sum.shape) != (d, n)):
+            raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
+        if log_prob and self.lp_acc is None:
+            raise ValueError("into= was begun without log_prob: its draws so far were not evaluated, so it cannot take log_prob up")
+        if lags is not None and self.lags != int(lags):
+            raise ValueError("into= was begun without these lags: the lagged products of its draws so far were not kept, so it "
+                             "cannot take them up")
+        if mixing is not None and self.mix_step is None:
+            raise ValueError("into= was begun without mixing: the steps and counts of its draws so far were not kept, so it "
+                             "cannot take them up")
+        if ladder is not None and self.ladder != ladder:
+            raise ValueError("into= was begun without log_z along these ladders: the ratios of its draws so far were not kept, so "
+                             "it cannot take them up")
+
     @property
     def n_targets(self):
         return int(self.acc.shape[0])
+
+    @property
+    def hist_rows(self):
+        """Rows of history the ring of `summarize` keeps before a window: the lags, one at least for the pair of a step."""
+        return max(self.lags or 0, 1) if self.mix_step is not None else self.lags or 0
+
+    @property
+    def hist_seen(self):
+        return 0 if self.hist is None else int(self.hist.shape[0])
+
+    def load_hist(self, ring, lp_ring):
+        """The rows an earlier call kept become the ring's first."""
+        if self.hist_seen:
+            ring[:self.hist_seen] = self.hist
+            if self.lp_acc is not None:
+                lp_ring[:self.hist_seen] = self.lp_hist[:, 0]
+
+    def store_hist(self, ring, lp_ring, rows):
+        """Keep these rows of the ring, oldest first, for the call that continues the summary."""
+        last = torch.tensor(rows, device=ring.device)
+        self.hist = ring[last]
+        if self.lp_acc is not None:
+            self.lp_hist = lp_ring[last][:, None, :]
+
+    def fold(self, ring, lp_ring, first, n_rows, n_hist, batch=None, scratch=None):
+        """Fold rows first .. first + n_rows of the contiguous ring (rows, d, n), behind the n_hist rows before them round the
+        ring's end, into every accumulator kept.  lp_ring (rows, n) receives their log-densities; batch = (library, handle, first
+        target) of the TargetBatch they are evaluated under; scratch: gsss_ladder_scratch_doubles(n_rows, n) doubles."""
+        x, m, L, n = ring[first:first + n_rows], self.chains_per_target, self.lags or 0, int(ring.shape[2])
+        target_moments(x, m, second_moment=self.second_moment, acc=self.acc, chain_sum=self.chain_sum)
+        if self.lp_acc is not None:
+            lib, handle, target0 = batch
+            lp, x, dev = lp_ring[first:first + n_rows], x.contiguous(), _device_index(ring)
+            with torch.cuda.device(dev):
+                _lib.check(lib.gsss_batch_logprob_draws(handle, x.data_ptr(), n_rows, n, target0, lp.data_ptr(),
+                                                        current_stream_ptr(dev)))
+            scalar_moments(lp, m, acc=self.lp_acc, chain_sum=self.lp_chain_sum)
+            self.update_best(lp, x)
+        if L:
+            _autocov_fold(ring, first, n_rows, min(L, n_hist), m, L, self.acov)
+            if self.lp_acov is not None:
+                _autocov_fold(lp_ring[:, None, :], first, n_rows, min(L, n_hist), m, L, self.lp_acov)
+        if self.mix_step is not None:
+            _mixing_fold(ring, first, n_rows, min(1, n_hist), m, self.mix_dirs, self.mix_modes, self.mix_transitions, self.mix_step,
+                         self.mix_counts)
+        if self.ladder is not None:
+            lib, handle, target0 = batch
+            _ladder_fold(handle, lib, x.contiguous(), n_rows, n, target0, self.ladder, scratch, self.ladder_acc)
 
     @property
     def ladder_hot_log_z(self):

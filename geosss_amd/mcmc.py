@@ -279,13 +279,16 @@ class RejectionSphericalSliceSampler:
         if not isinstance(exchange, dict) or set(exchange) - {"ladder", "every"} or "ladder" not in exchange:
             raise ValueError("exchange must be dict(ladder=R, every=k)")
         R, k = int(exchange["ladder"]), int(exchange.get("every", 1))
-        M = self.n_chains // self._batch_m
-        if R < 2 or M % R or (self.chain_offset // self._batch_m) % R:
-            raise ValueError(f"the {M} targets of this sampler (from target {self.chain_offset // self._batch_m} on) are no run of "
-                             f"whole ladders of {R} members (ladder >= 2)")
+        self._check_whole_ladders(R)
         if k < 1:
             raise ValueError(f"every must be >= 1 (got {k})")
         return R, k
+
+    def _check_whole_ladders(self, R):
+        M, t0 = self.n_chains // self._batch_m, self.chain_offset // self._batch_m
+        if R < 2 or M % R or t0 % R:
+            raise ValueError(f"the {M} targets of this sampler (from target {t0} on) are no run of whole ladders of {R} members "
+                             "(ladder >= 2)")
 
     @contextlib.contextmanager
     def _exchanging(self, exchange):
@@ -371,11 +374,24 @@ class RejectionSphericalSliceSampler:
         if active is not None and R != active:
             raise ValueError(f"log_z= and exchange= name different ladders ({R} and {active} members): the ratios are taken "
                              "between the members that exchange")
-        M = self.n_chains // self._batch_m
-        if R < 2 or M % R or (self.chain_offset // self._batch_m) % R:
-            raise ValueError(f"the {M} targets of this sampler (from target {self.chain_offset // self._batch_m} on) are no run of "
-                             f"whole ladders of {R} members (ladder >= 2)")
+        self._check_whole_ladders(R)
         return R
+
+    def _mixing_plan(self, mixing):
+        """dict(hop, modes, weights, transitions) of summarize(mixing=True | dict(..)) for this sampler's targets, and the
+        refusals."""
+        if mixing is True:
+            if self._batch_m is None:
+                raise ValueError("summarize(mixing=True) takes the directions of a TargetBatch's members: pass "
+                                 "mixing=dict(hop=, modes=, weights=) for a single target")
+            t0 = self.chain_offset // self._batch_m
+            t = slice(t0, t0 + self.n_chains // self._batch_m)
+            hop, modes, weights = self.target.mixing_directions()
+            return {"hop": hop[t], "modes": modes[t], "weights": None if weights is None else weights[t], "transitions": False}
+        if isinstance(mixing, dict) and not set(mixing) - {"hop", "modes", "weights", "transitions"}:
+            return {"hop": mixing.get("hop"), "modes": mixing.get("modes"), "weights": mixing.get("weights"),
+                    "transitions": bool(mixing.get("transitions", False))}
+        raise ValueError("mixing must be True or a dict with the keys hop, modes, weights, transitions")
 
     def _advance_exchanging(self, n_steps, plan, thin, out, replay, chain_major, row0, keep):
         """advance() cut at the sweep points.  Rows are kept at the call's steps thin, 2 thin, ..: a piece that starts on one of
@@ -813,9 +829,8 @@ class RejectionSphericalSliceSampler:
         log_prob=True (a TargetBatch sampler): every window, draw 0 included, is also evaluated under the targets that own its
         chains (gsss_batch_logprob_draws, one launch) into one reused (window, n) buffer, which is folded into `lp_acc` and
         `lp_chain_sum` (gsss_scalar_moments) and into the running best draw per target, `lp_best` / `x_best` -- the MAP estimate
-        among the retained draws; stats() then reports lp_mean, lp_var, lp_rhat, lp_ess_between, lp_best, x_best.  into=
-        continues them too (a summary that carries them goes on carrying them); one begun without cannot take them up.  The
-        moments, the chains and the launches of the default are untouched by it.
+        among the retained draws.  into= continues them too (a summary that carries them goes on carrying them); one begun
+        without cannot take them up.  The moments, the chains and the launches of the default are untouched by it.
 
         lags=L (1 .. 64): also the within-chain autocorrelation of every coordinate, the estimator that needs no more than a few
         chains per target.  The one reused buffer becomes a ring of L + window rows -- L d n 8 bytes more than the windows need;
@@ -823,13 +838,11 @@ class RejectionSphericalSliceSampler:
         the windows are written one behind the other, cut so that none wraps; every window is folded by gsss_target_autocov
         beside the moments fold, its L rows of history read where they lie in the ring.  (Every fold reads its L rows of
         history: where 256 MiB leave windows of a row or two -- 10^6 chains -- pass window=L or more, a ring of 2 L rows, and
-        the lags cost a few ms; DESIGN.md §5.6g has the figures.)  The result carries `acov`
-        (M, d, L + 1, 3) and the ring's last L rows, from which into= goes on; stats() adds acf (M, d, L + 1), iat, ess_within
-        = m n / iat and iat_truncated (diagnostics.from_target_autocov).  With log_prob=True the value buffer becomes a ring too
-        and the log-density series is folded the same way: lp_acf, lp_iat, lp_ess_within, lp_iat_truncated.  n_samples <= L is
-        refused; a summary begun without lags cannot take them up.  The chains, the final state and -- window for window -- the
-        moments are those of the default; where the ring's end cuts a window that the default would not cut, acc and chain_sum
-        may differ from the default's in the last bits (per-window partial sums are added).
+        the lags cost a few ms; DESIGN.md §5.6g has the figures.)  The result keeps the ring's last L rows, from which into=
+        goes on.  With log_prob=True the value buffer becomes a ring too and the log-density series is folded the same way.
+        n_samples <= L is refused; a summary begun without lags cannot take them up.  The chains, the final state and -- window
+        for window -- the moments are those of the default; where the ring's end cuts a window that the default would not cut,
+        acc and chain_sum may differ from the default's in the last bits (per-window partial sums are added).
 
         mixing=True (a TargetBatch sampler) or mixing=dict(hop=, modes=, weights=, transitions=) (any sampler): also what the
         paper judges a sampler by, per target and against the target's OWN directions -- the mean geodesic step between
@@ -838,10 +851,8 @@ class RejectionSphericalSliceSampler:
         `TargetBatch.mixing_directions()` of the targets this sampler samples; the dict's hop is (d,) or (M, d), its modes (K, d)
         or (M, K, d), its weights (K,) or (M, K), for the M targets of this sampler.  The buffer becomes a ring with at least
         one row of history (max(lags, 1) + window rows) and every window is folded by gsss_target_mixing beside the other
-        folds.  The result carries `mix_step`, `mix_counts`, `mix_modes`, `mix_weights`; stats() adds geodesic_step,
-        geodesic_step_sd, hop_frequency, mode_occupancy, mode_kl (with weights) and, with transitions=True, mode_transitions
-        and mode_switch_frequency (diagnostics.from_target_mixing).  into= continues them with the directions they were begun
-        with, the pair at the seam counted once; a summary begun without mixing cannot take it up.
+        folds; transitions=True also counts the pairs by [mode before][mode after].  into= continues them with the directions
+        they were begun with, the pair at the seam counted once; a summary begun without mixing cannot take it up.
 
         exchange=dict(ladder=R, every=k): replica exchange as in `advance`, during burn-in and between the retained draws; k must
         be a multiple of thin.  With mixing=True this is the remedy for the targets that `hop_frequency == 0` finds.
@@ -852,12 +863,11 @@ class RejectionSphericalSliceSampler:
         columns, then the fold into ten doubles per pair of chains; `diagnostics.target_ladder`).  True takes the ladder from
         exchange= if given, else from `batch.ladder` (set by `tempered`), else raises ValueError; a ladder that differs from
         exchange='s is refused.  With exchange= the retained row is the state before the sweep, which has rung r's law either
-        way.  The result carries `ladder`, `ladder_acc` (G, R - 1, m, 10) and `ladder_hot_log_z` (`TargetBatch.hot_log_z`);
-        stats() adds log_z_ratio -- the forward (stepping-stone) estimate from the hotter member's draws; the backward one is
-        reported as a consistency check, not averaged in --, log_z_ratio_forward, log_z_ratio_backward, log_z_lower,
-        log_z_upper, log_z_ratio_se, used, skipped, log_z (G, R) and hot_log_z (`diagnostics.from_target_ladder`).  into=
-        continues the sums; a summary begun without log_z cannot take it up.  The moments, the chains and the other launches
-        are untouched by it."""
+        way.  into= continues the sums; a summary begun without log_z cannot take it up.  The moments, the chains and the
+        other launches are untouched by it.
+
+        What each feature keeps on the result and what stats() reports for it: `diagnostics.TargetMoments`.  Where the windows
+        lie in the buffer: `diagnostics.ring_plan`."""
         if exchange is not None:
             if log_z is not None and log_z is not False:      # (refused before the exchange buffers are made)
                 self._ladder_plan(log_z, self._exchange_plan(exchange)[0])
@@ -873,164 +883,63 @@ class RejectionSphericalSliceSampler:
         if thin < 1:
             raise ValueError("thin must be >= 1")
         n, d = self.n_chains, self.d
-        if self._batch_m is not None:
-            if chains_per_target is not None and int(chains_per_target) != self._batch_m:
-                raise ValueError(f"this sampler's TargetBatch has {self._batch_m} chains per target")
-            m = self._batch_m
-        else:
-            m = n if chains_per_target is None else int(chains_per_target)
+        m = self._batch_m or (n if chains_per_target is None else int(chains_per_target))
+        if self._batch_m is not None and chains_per_target is not None and int(chains_per_target) != m:
+            raise ValueError(f"this sampler's TargetBatch has {m} chains per target")
         if m < 1 or n % m:
             raise ValueError(f"n_chains ({n}) must be a multiple of chains_per_target ({m})")
         if log_prob and self._batch_m is None:
             raise ValueError("summarize(log_prob=True) evaluates the draws with the batch kernel: wrap the target in a TargetBatch "
                              "of one (TargetBatch([pdf]), chains_per_target = n_chains)")
-        ladder = None
+        asked = {"second_moment": second_moment, "log_prob": bool(log_prob), "lags": lags, "mixing": None, "ladder": None}
         if log_z is not None and log_z is not False:
-            ladder = self._ladder_plan(log_z, self._exchange_active[0] if self._exchange_active else None)
+            asked["ladder"] = self._ladder_plan(log_z, self._exchange_active[0] if self._exchange_active else None)
         if lags is not None:
             if not 1 <= int(lags) <= 64:
                 raise ValueError(f"lags must be 1 .. 64 (got {lags})")
             if into is None and int(n_samples) <= int(lags):
                 raise ValueError(f"the autocorrelation needs more than `lags` retained draws per chain (n_samples = {n_samples}, "
                                  f"lags = {lags})")
-        mix = None
         if mixing is not None and mixing is not False:
-            if mixing is True:
-                if self._batch_m is None:
-                    raise ValueError("summarize(mixing=True) takes the directions of a TargetBatch's members: pass "
-                                     "mixing=dict(hop=, modes=, weights=) for a single target")
-                t0 = self.chain_offset // m
-                hop, modes, weights = self.target.mixing_directions()
-                mix = {"hop": hop[t0:t0 + n // m], "modes": modes[t0:t0 + n // m],
-                       "weights": None if weights is None else weights[t0:t0 + n // m], "transitions": False}
-            elif isinstance(mixing, dict) and not set(mixing) - {"hop", "modes", "weights", "transitions"}:
-                mix = {"hop": mixing.get("hop"), "modes": mixing.get("modes"), "weights": mixing.get("weights"),
-                       "transitions": bool(mixing.get("transitions", False))}
-            else:
-                raise ValueError("mixing must be True or a dict with the keys hop, modes, weights, transitions")
-        full, rows = diagnostics._moments_form(d, second_moment if into is None or second_moment is not None else into.second_moment)
+            asked["mixing"] = self._mixing_plan(mixing)
         if into is None:
-            into = diagnostics.TargetMoments(torch.zeros((n // m, rows), dtype=torch.float64, device=self._tdev),
-                                             torch.zeros((d, n), dtype=torch.float64, device=self._tdev), d, m, full)
-            if log_prob:
-                into.lp_acc = torch.zeros((n // m, 3), dtype=torch.float64, device=self._tdev)
-                into.lp_chain_sum = torch.zeros(n, dtype=torch.float64, device=self._tdev)
-                into.lp_best = torch.full((n // m,), float("-inf"), dtype=torch.float64, device=self._tdev)
-                into.x_best = torch.zeros((n // m, d), dtype=torch.float64, device=self._tdev)
-            if lags is not None:
-                into.lags = int(lags)
-                into.acov = torch.zeros((n // m, d, into.lags + 1, 3), dtype=torch.float64, device=self._tdev)
-                if log_prob:
-                    into.lp_acov = torch.zeros((n // m, 1, into.lags + 1, 3), dtype=torch.float64, device=self._tdev)
-            if mix is not None:
-                into.mix_dirs, into.mix_modes = diagnostics._mixing_dirs(mix["hop"], mix["modes"], n // m, d, self._tdev)
-                into.mix_transitions = mix["transitions"]
-                if mix["weights"] is not None:
-                    w = diagnostics._t(mix["weights"]).to(torch.float64)
-                    w = w[None].expand(n // m, -1) if w.ndim == 1 else w
-                    if into.mix_modes == 0 or tuple(w.shape) != (n // m, into.mix_modes):
-                        raise ValueError(f"weights must be (K,) or (M, K) = ({n // m}, {into.mix_modes}), one per mode direction")
-                    into.mix_weights = w.contiguous().to(self._tdev)
-                cols = 3 + into.mix_modes + (into.mix_modes ** 2 if into.mix_transitions else 0)
-                into.mix_step = torch.zeros((n // m, 2), dtype=torch.float64, device=self._tdev)
-                into.mix_counts = torch.zeros((n // m, cols), dtype=torch.int64, device=self._tdev)
-            if ladder is not None:
-                g0 = self.chain_offset // m // ladder
-                into.ladder = ladder
-                into.ladder_acc = torch.zeros((n // m // ladder, ladder - 1, m, diagnostics.LADDER_SLOTS), dtype=torch.float64,
-                                              device=self._tdev)
-                into._ladder_source = (self.target, g0)         # (hot_log_z is read from the batch when stats() asks for it)
-        elif (into.d != d or into.chains_per_target != m or into.second_moment != full or tuple(into.acc.shape) != (n // m, rows)
-              or tuple(into.chain_sum.shape) != (d, n)):
-            raise ValueError("into= continues a summary of the same chains, chains_per_target and second-moment form")
-        elif log_prob and into.lp_acc is None:
-            raise ValueError("into= was begun without log_prob: its draws so far were not evaluated, so it cannot take log_prob up")
-        elif lags is not None and into.lags != int(lags):
-            raise ValueError("into= was begun without these lags: the lagged products of its draws so far were not kept, so it "
-                             "cannot take them up")
-        elif mix is not None and into.mix_step is None:
-            raise ValueError("into= was begun without mixing: the steps and counts of its draws so far were not kept, so it "
-                             "cannot take them up")
-        elif ladder is not None and into.ladder != ladder:
-            raise ValueError("into= was begun without log_z along these ladders: the ratios of its draws so far were not kept, so "
-                             "it cannot take them up")
-        ladder = into.ladder
-        lz_scratch = None
-        log_prob = into.lp_acc is not None
-        mixing = into.mix_step is not None
-        L = into.lags or 0
-        H = max(L, 1) if mixing else L                # rows of history the ring keeps
-        rest = int(n_samples) - 1
+            tm = diagnostics.TargetMoments.begin(n, d, m, self._tdev, **asked,
+                                                 ladder_source=(self.target, self.chain_offset // m // (asked["ladder"] or 1)))
+        else:
+            tm = into
+            tm.check_continues(n, d, m, **asked)
+        H, rest = tm.hist_rows, int(n_samples) - 1
         if window is None:                            # (with lags the ring of L + window rows is what stays under 256 MiB)
             window = max(1, (256 << 20) // (8 * d * n) - H)
-        window = int(window)
-        if window < 1:
+        if int(window) < 1:
             raise ValueError("window must be >= 1")
-        window = max(1, min(window, rest))
+        window = max(1, min(int(window), rest))
+        rows, draw0, windows, keep = diagnostics.ring_plan(rest, window, H, tm.hist_seen)
         steps0 = self._step
         if burnin:
             self.advance(burnin)
 
-        rows = H + window
-        lp_buf = torch.empty((rows, n), dtype=torch.float64, device=self._tdev) if log_prob else None
-        buf = torch.empty((rows, d, n), dtype=torch.float64, device=self._tdev) if rest or H else None
-        if ladder is not None:
-            lz_scratch = torch.empty(int(self._lib.gsss_ladder_scratch_doubles(window, n)), dtype=torch.float64, device=self._tdev)
-
-        def fold(x, first=0, hist=0):
-            """x: a window (w, d, n); with lags it is the rows first .. of the ring, behind `hist` rows of history"""
-            w = int(x.shape[0])
-            lp = lp_buf[first:first + w] if log_prob else None
-            diagnostics.target_moments(x, m, second_moment=full, acc=into.acc, chain_sum=into.chain_sum)
-            if log_prob:
-                x = x.contiguous()
-                with torch.cuda.device(self.device):
-                    _lib.check(self._lib.gsss_batch_logprob_draws(self._target_dev.handle, x.data_ptr(), w, n, self.chain_offset // m,
-                                                                  lp.data_ptr(), current_stream_ptr(self.device)))
-                diagnostics.scalar_moments(lp, m, acc=into.lp_acc, chain_sum=into.lp_chain_sum)
-                into.update_best(lp, x)
-            if L:
-                diagnostics._autocov_fold(buf, first, w, min(L, hist), m, L, into.acov)
-                if log_prob:
-                    diagnostics._autocov_fold(lp_buf[:, None, :], first, w, min(L, hist), m, L, into.lp_acov)
-            if mixing:
-                diagnostics._mixing_fold(buf, first, w, min(1, hist), m, into.mix_dirs, into.mix_modes, into.mix_transitions,
-                                         into.mix_step, into.mix_counts)
-            if ladder is not None:
-                diagnostics._ladder_fold(self._target_dev.handle, self._lib, x.contiguous(), w, n, self.chain_offset // m, ladder,
-                                         lz_scratch, into.ladder_acc)
-
-        if not H:
-            fold(self._state[None])                   # draw 0: the state itself is a (1, d, n) window
-            done = 0
-            while done < rest:
-                w = min(window, rest - done)
-                fold(self.advance(w * thin, thin=thin, out=buf[:w]))
-                done += w
-        else:
-            # The ring: the rows kept by an earlier call, draw 0, then window after window, none of which wraps; the H rows
-            # before a window (round the ring's end) are the L draws before it, where the kernel reads them.
-            seen = 0 if into.hist is None else int(into.hist.shape[0])
-            if seen:
-                buf[:seen] = into.hist
-                if log_prob:
-                    lp_buf[:seen] = into.lp_hist[:, 0]
-            buf[seen] = self._state
-            fold(buf[seen:seen + 1], seen, seen)
-            pos, seen, done = seen + 1, seen + 1, 0
-            while done < rest:
-                pos %= rows
-                w = min(window, rest - done, rows - pos)
-                fold(self.advance(w * thin, thin=thin, out=buf[pos:pos + w]), pos, min(H, seen))
-                pos, seen, done = pos + w, seen + w, done + w
-            last = (pos - min(H, seen) + torch.arange(min(H, seen), device=self._tdev)) % rows
-            into.hist = buf[last]
-            if log_prob:
-                into.lp_hist = lp_buf[last][:, None, :]
+        def empty(*shape):
+            return torch.empty(shape, dtype=torch.float64, device=self._tdev)
+        lp_buf = empty(rows, n) if tm.lp_acc is not None else None
+        buf = empty(rows, d, n) if rest or H else None
+        scratch = empty(int(self._lib.gsss_ladder_scratch_doubles(window, n))) if tm.ladder is not None else None
+        batch = (self._lib, self._target_dev.handle, self.chain_offset // m) if self._batch_m is not None else None
+        if draw0 is None:                             # no history: the state itself is a (1, d, n) window
+            tm.fold(self._state[None], lp_buf, 0, 1, 0, batch, scratch)
+        else:                                         # the rows an earlier call kept, then draw 0 behind them
+            tm.load_hist(buf, lp_buf)
+            buf[draw0[0]] = self._state
+            tm.fold(buf, lp_buf, *draw0, batch, scratch)
+        for first, w, n_hist in windows:
+            self.advance(w * thin, thin=thin, out=buf[first:first + w])
+            tm.fold(buf, lp_buf, first, w, n_hist, batch, scratch)
+        if keep:
+            tm.store_hist(buf, lp_buf, keep)
         self._account_calls(self._step - steps0)
         self._check_errors()
         self._sync_rng()
-        return into
+        return tm
 
     def _sample_rows(self, out, skip, n_rows, thin):
         """burn-in, row 0 = the state after it, then the kept rows, written straight into `out` (chains, draws, dims)."""

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import geosss_amd as gs
+from geosss_amd import diagnostics
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
@@ -122,6 +123,75 @@ def test_summarize_is_the_stored_run_summed(which):
     # running statistics still refuse a batch
     with pytest.raises(ValueError):
         s.enable_stats()
+
+
+def test_summarize_is_the_public_functions_along_the_ring_plan():
+    """Every feature at once, 23 draws in three calls chained with into= (windows cut by the ring's end, seams that carry
+    history): the accumulators are, bit for bit, what target_moments, target_log_prob + scalar_moments + best_draw,
+    target_autocov, target_mixing and target_ladder give on the stored draws of a twin, applied window by window as
+    diagnostics.ring_plan cuts them, behind the same rows of history."""
+    d, m, R, L, window = 3, 8, 2, 4, 5
+    g = np.random.default_rng(23)
+    base = []
+    for _ in range(2):
+        mu = g.standard_normal((2, d))
+        mu *= (10.0 + 30.0 * g.random((2, 1))) / np.linalg.norm(mu, axis=1, keepdims=True)
+        base.append(gs.MixtureModel([gs.VonMisesFisher(v) for v in mu], g.random(2) + 0.5))
+    batch = gs.TargetBatch.tempered(base, [1.0, 0.5])
+    M, n = len(batch), len(batch) * m
+    assert M == 4 and batch.ladder == R
+    hop, modes, weights = batch.mixing_directions()
+    mix = dict(hop=hop, modes=modes, weights=weights, transitions=True)
+    K = modes.shape[1]
+    x0, ex, calls = _x0(d, n, seed=9), dict(ladder=R, every=2), (8, 8, 7)
+
+    def make():
+        return gs.ShrinkageSphericalSliceSampler(batch, x0, SEED, chains_per_target=m)
+    twin = make()
+    x = twin.sample(sum(calls), burnin=3, thin=2, as_tensor=True, exchange=ex).permute(1, 2, 0).contiguous()      # (23, d, n)
+
+    s, tm = make(), None
+    for i, n_samples in enumerate(calls):
+        tm = s.summarize(n_samples, burnin=2 if i else 3, thin=2, window=window, lags=L, log_prob=True, mixing=mix, log_z=True,
+                         exchange=ex, into=tm)
+
+    def zeros(*shape, dtype=torch.float64):
+        return torch.zeros(shape, dtype=dtype, device="cuda")
+    acc, chain_sum, lp_acc, lp_chain_sum = zeros(M, 1 + d + d * (d + 1) // 2), zeros(d, n), zeros(M, 3), zeros(n)
+    lp_best, x_best = torch.full((M,), float("-inf"), dtype=torch.float64, device="cuda"), zeros(M, d)
+    acov, lp_acov, step = zeros(M, d, L + 1, 3), zeros(M, 1, L + 1, 3), zeros(M, 2)
+    counts, ladder_acc = zeros(M, 3 + K + K * K, dtype=torch.int64), zeros(M // R, R - 1, m, diagnostics.LADDER_SLOTS)
+    lp_all = zeros(sum(calls), n)
+    at, cut_by_the_end = 0, 0
+    for n_samples in calls:
+        rows, draw0, windows, keep = diagnostics.ring_plan(n_samples - 1, window, L, min(L, at))
+        assert rows == L + window and draw0 == (min(L, at), 1, min(L, at))
+        for first, w, h in [draw0] + windows:
+            cut_by_the_end += first + w == rows and w < window
+            xw = x[at:at + w]
+            diagnostics.target_moments(xw, m, acc=acc, chain_sum=chain_sum)
+            lp = lp_all[at:at + w] = diagnostics.target_log_prob(batch, xw)
+            diagnostics.scalar_moments(lp, m, acc=lp_acc, chain_sum=lp_chain_sum)
+            best, row, chain = diagnostics.best_draw(lp, m)
+            better = best > lp_best                                   # (strictly: the earliest of equal draws stays)
+            lp_best, x_best = torch.where(better, best, lp_best), torch.where(better[:, None], xw[row, :, chain], x_best)
+            diagnostics.target_autocov(xw, m, L, acc=acov, hist=x[at - h:at])
+            diagnostics.target_autocov(lp, m, L, acc=lp_acov, hist=lp_all[at - h:at])
+            diagnostics.target_mixing(xw, m, hop=hop, modes=modes, transitions=True, step=step, counts=counts,
+                                      hist=x[at - min(1, h):at])
+            diagnostics.target_ladder(batch, xw, R, acc=ladder_acc)
+            at += w
+    assert at == sum(calls) and cut_by_the_end >= 2
+    for name, want in (("acc", acc), ("chain_sum", chain_sum), ("lp_acc", lp_acc), ("lp_chain_sum", lp_chain_sum),
+                       ("lp_best", lp_best), ("x_best", x_best), ("mix_counts", counts), ("ladder_acc", ladder_acc),
+                       ("hist", x[-L:]), ("lp_hist", lp_all[-L:, None, :]), ("acov", acov), ("lp_acov", lp_acov),
+                       ("mix_step", step)):
+        got = getattr(tm, name)
+        differ = int((got != want).sum())
+        print(f"{name}: {differ} of {want.numel()} entries differ")
+        assert got.shape == want.shape and got.dtype == want.dtype and torch.equal(got, want), name
+    assert float(acc[:, 0].min()) == m * sum(calls) and int(counts[:, 1].min()) == m * (sum(calls) - 1)
+    assert torch.equal(s.state_rows(), twin.state_rows()) and s._step == twin._step == 3 + 2 * (sum(calls) - 1)
 
 
 def test_pooled_vmf_mean_and_rhat():
