@@ -64,6 +64,15 @@ def main():
         x, dt = chains(method, pdf, x0, m)
         hop = float(dg.hopping_frequency(x, pdf.mode).mean())
         print(f"  {method:10s} hopping frequency {hop:8.4f}   ESS(x_1) {ess_first_coordinate(x):8.1f}   {dt:5.2f} s")
+    # The distribution of u_d^T x (the paper's Fig. 2; np.histogram(vals, bins=100) in scripts/Bingham.ipynb) without stored
+    # draws: the slice samplers count it on the device while they run.  Both modes +-u_d should hold half of the mass.
+    print("  u_d^T x in 100 bins, from summarize(marginals=...):")
+    for method in ("sss-reject", "sss-shrink"):
+        tm = METHODS[method](pdf, x0, 3521).summarize(m, burnin=0.2, marginals=dict(bins=100, directions=pdf.mode[None]))
+        hist = tm.marg_counts[0, 0].cpu().numpy()
+        lo, med, hi = (float(v) for v in tm.quantile([0.025, 0.5, 0.975])[0, 0])
+        print(f"  {method:10s} mass at u < 0 {hist[:50].sum() / hist.sum():6.3f}   at |u| > 0.8 {(hist[:10].sum() + hist[90:].sum()) / hist.sum():6.3f}"
+              f"   median {med:+.3f}   95 % interval [{lo:+.3f}, {hi:+.3f}]")
 
     for d in (3, 10):
         pdf = gs.CurvedVonMisesFisher(gs.SlerpCurve(gs.brownian_curve(n_points=10, dimension=d, step_size=0.5, seed=4562)), 800.0)

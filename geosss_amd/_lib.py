@@ -16,6 +16,7 @@ ABI_VERSION = 10
 STATS_NO_SECOND_MOMENT = 1
 MOMENTS_DIAG = 1
 MIXING_TRANSITIONS = 1
+MARGINALS_STEP = 1
 
 
 class GsssError(RuntimeError):
@@ -76,6 +77,9 @@ SIGNATURES = {
     "gsss_mixing_rows": (C.c_int64, [C.c_int32, C.c_int32]),
     "gsss_target_mixing": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gsss_marginal_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gsss_target_marginals": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "gsss_exchange_scratch_doubles": (C.c_int64, [C.c_int64]),
     "gsss_batch_exchange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_uint64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,6 +17,7 @@
 #include "gsss_launch.h"
 #include "gsss_mh.h"
 #include "gsss_autocov.h"
+#include "gsss_marginals.h"
 #include "gsss_mixing.h"
 #include "gsss_moments.h"
 #include "gsss_user_target.h"
@@ -1681,6 +1682,61 @@ int gsss_target_mixing(const double *ring_dev, int64_t ring_rows, int64_t first_
     if (!guard.ok) return GSSS_E_HIP;
     return launch_target_mixing(ring_dev, ring_rows, first_row, n_rows, n_hist, n_chains, d, chains_per_target, dirs_dev, n_modes,
                                 (flags & GSSS_MIXING_TRANSITIONS) != 0, step_dev, count_dev, static_cast<hipStream_t>(stream));
+}
+
+// The shape of a target's histograms: GSSS_OK, or the code gsss_marginal_rows returns (message set for `entry`).
+static int check_marginal_shape(const char *entry, int32_t n_dirs, int32_t n_bins, int32_t flags)
+{
+    const bool steps = (flags & GSSS_MARGINALS_STEP) != 0;
+    if (n_dirs < 0 || (n_dirs == 0 && !steps) || n_bins < 2 || (flags & ~GSSS_MARGINALS_STEP)) {
+        set_error("%s: need n_dirs >= 0 (>= 1 without GSSS_MARGINALS_STEP), n_bins >= 2 and known flags (n_dirs = %d, n_bins = %d, "
+                  "flags = %d)", entry, n_dirs, n_bins, flags);
+        return GSSS_E_INVALID;
+    }
+    if (n_dirs > kMarginalsMaxDirs || n_bins > kMarginalsMaxBins || marginal_series(n_dirs, steps) * n_bins > kMarginalsMaxCounters) {
+        set_error("%s: at most %d directions, %d bins and %d counters per target are kept (n_dirs = %d, n_bins = %d: %lld counters)",
+                  entry, kMarginalsMaxDirs, kMarginalsMaxBins, kMarginalsMaxCounters, n_dirs, n_bins,
+                  (long long)(marginal_series(n_dirs, steps) * n_bins));
+        return GSSS_E_UNSUPPORTED;
+    }
+    return GSSS_OK;
+}
+
+int64_t gsss_marginal_rows(int32_t n_dirs, int32_t n_bins, int32_t flags)
+{
+    if (int rc = check_marginal_shape("gsss_marginal_rows", n_dirs, n_bins, flags)) return rc;
+    return marginal_series(n_dirs, (flags & GSSS_MARGINALS_STEP) != 0) * n_bins;
+}
+
+int gsss_target_marginals(const double *ring_dev, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist,
+                          int64_t n_chains, int32_t d, int64_t chains_per_target, const double *dirs_dev, int32_t n_dirs,
+                          int32_t n_bins, int32_t flags, int64_t *count_dev, int device, void *stream)
+{
+    if (d < 2) {
+        set_error("gsss_target_marginals: need d >= 2 (d = %d)", d);
+        return GSSS_E_INVALID;
+    }
+    if (int rc = check_chains_per_target("gsss_target_marginals", n_chains, chains_per_target)) return rc;
+    if (int rc = check_ring("gsss_target_marginals", ring_rows, first_row, n_rows, n_hist)) return rc;
+    if (n_hist > 1 || n_hist > ring_rows - n_rows) {
+        set_error("gsss_target_marginals: n_hist (%lld) exceeds the one row of history or the ring's rows outside the block (%lld)",
+                  (long long)n_hist, (long long)(ring_rows - n_rows));
+        return GSSS_E_INVALID;
+    }
+    if (int rc = check_marginal_shape("gsss_target_marginals", n_dirs, n_bins, flags)) return rc;
+    if (n_rows > kMarginalsMaxRows) {
+        set_error("gsss_target_marginals: a block has at most 2^23 rows (n_rows = %lld): fold it in several calls", (long long)n_rows);
+        return GSSS_E_UNSUPPORTED;
+    }
+    if (n_rows == 0 || n_chains == 0) return GSSS_OK;
+    if (!ring_dev || !count_dev || (n_dirs > 0 && !dirs_dev)) {
+        set_error("gsss_target_marginals: %s is null", !ring_dev ? "ring_dev" : (!count_dev ? "count_dev" : "dirs_dev"));
+        return GSSS_E_INVALID;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return GSSS_E_HIP;
+    return launch_target_marginals(ring_dev, ring_rows, first_row, n_rows, n_hist, n_chains, d, chains_per_target, dirs_dev, n_dirs,
+                                   n_bins, (flags & GSSS_MARGINALS_STEP) != 0, count_dev, static_cast<hipStream_t>(stream));
 }
 
 int gsss_mode_supported(const gsss_target *t, int32_t mode)

@@ -20,7 +20,7 @@ from .sphere import current_stream_ptr
 __all__ = ["acf", "acf_fft", "IAT", "n_eff", "distance", "hopping_frequency", "mode_occupancy", "mode_kl", "from_running",
            "iat_from_acf", "ess_bulk", "ess_between_chains", "target_moments", "from_target_moments", "TargetMoments",
            "target_log_prob", "scalar_moments", "from_scalar_moments", "best_draw", "target_autocov", "from_target_autocov",
-           "target_mixing", "from_target_mixing", "ring_plan"]
+           "target_mixing", "from_target_mixing", "target_marginals", "from_target_marginals", "marginal_quantile", "ring_plan"]
 
 
 def _t(x):
@@ -662,6 +662,173 @@ def from_target_mixing(step, counts, n_modes, *, weights=None):
     return out
 
 
+MARGINAL_QUANTILES = (0.025, 0.25, 0.5, 0.75, 0.975)  # what stats() reports of every marginal: median, quartiles, 95 % interval
+
+
+def _marginals_plan(marginals):
+    """dict(bins, directions, steps) of summarize(marginals=True | dict(..)), and the refusals that need no device."""
+    if marginals is True:
+        return {"bins": 64, "directions": None, "steps": False}
+    if isinstance(marginals, dict) and not set(marginals) - {"bins", "directions", "steps"}:
+        plan = {"bins": marginals.get("bins", 64), "directions": marginals.get("directions"),
+                "steps": bool(marginals.get("steps", False))}
+        _marginal_bins(plan["bins"])
+        return plan
+    raise ValueError("marginals must be True or a dict with the keys bins, directions, steps")
+
+
+def _marginal_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= 1024:
+        raise ValueError(f"bins must be a whole number 2 .. 1024 (got {bins!r})")
+    return int(bins)
+
+
+def _marginal_shape(bins, n_dirs, steps):
+    """B, after the refusals of gsss_marginal_rows."""
+    B, S = _marginal_bins(bins), n_dirs + (1 if steps else 0)
+    if n_dirs > 32:
+        raise ValueError(f"at most 32 directions per target are kept (got {n_dirs})")
+    if S == 0:
+        raise ValueError("no directions and no steps: there is nothing to count")
+    if S * B > 8192:
+        raise ValueError(f"at most 8192 counters per target are kept ({S} series of {B} bins are {S * B})")
+    return B
+
+
+def _marginal_dirs(directions, M, d, device):
+    """(dirs (M, P, d) contiguous float64 on `device`, P) from directions (P, d) | (M, P, d) | None: the shared form is broadcast,
+    None is the d coordinate axes."""
+    if directions is None:
+        v = torch.eye(d, dtype=torch.float64)
+    else:
+        try:
+            v = _t(directions).to(torch.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError("directions must be an array of directions") from e
+    if v.ndim == 2:
+        v = v[None].expand(M, -1, -1)
+    if v.ndim != 3 or v.shape[0] != M or v.shape[2] != d:
+        raise ValueError(f"directions must be (P, {d}) or ({M}, P, {d}) (got {tuple(_t(directions).shape)})")
+    return v.to(device).contiguous(), int(v.shape[1])
+
+
+def _n_marginal_dirs(directions, d):
+    """P of `_marginal_dirs` without building them."""
+    if directions is None:
+        return d
+    shape = tuple(directions.shape) if hasattr(directions, "shape") else np.shape(directions)
+    return int(shape[-2]) if len(shape) >= 2 else -1
+
+
+def target_marginals(x, chains_per_target, *, bins=64, directions=None, steps=False, chain_major=False, counts=None, hist=None):
+    """Per-target marginal histograms of a block of draws on the device, in one pass (gsss_target_marginals, include/gsss.h),
+    every target with its own directions.
+
+    x: a CUDA float64 tensor, component-major (R, d, n) -- what `advance(..., thin=t)` returns -- or, with chain_major=True,
+    (n, R, d) -- what `sample(..., as_tensor=True)` returns.  Target t owns the chains [t m, (t + 1) m), m = chains_per_target,
+    M = n / m.  directions: (P, d) for every target or (M, P, d), P <= 32, unit vectors or not (None: the d coordinate axes).
+    Returns counts (M, S, B) int64, B = bins (2 .. 1024), S = P + (1 if steps else 0), S B <= 8192: series p < P counts the target's
+    draws by u = x . v_p over B equal bins of [-1, 1] -- bin floor((u + 1) B / 2), what falls outside in the first and the last
+    bin; with steps=True series P counts its pairs of consecutive draws by theta = arccos(clip(x_r . x_{r-1}, -1, 1)) over B
+    equal bins of [0, pi].  NaN is counted nowhere.  `hist`: the one row that precedes x, laid out like x ((1, d, n), chain-major
+    (n, 1, d)), for a caller who streams a series block by block with steps; `counts` continues an earlier result (added to,
+    returned).  -> `from_target_marginals`."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.ndim != 3:
+        raise ValueError("x must be a CUDA float64 tensor (R, d, n), or (n, R, d) with chain_major=True")
+
+    def rows_first(t):
+        return t.permute(1, 2, 0) if chain_major else t
+    R, d, n = (int(v) for v in rows_first(x).shape)
+    m = _chains_per_target(chains_per_target, n)
+    if d < 2:
+        raise ValueError("a point on a sphere has two coordinates at least")
+    M, h = n // m, 0
+    dirs, P = _marginal_dirs(directions, M, d, x.device)
+    B = _marginal_shape(bins, P, steps)
+    if not x.is_cuda:
+        raise ValueError("x must be a CUDA float64 tensor: the counts are taken on the device")
+    if hist is not None:
+        if (not isinstance(hist, torch.Tensor) or hist.ndim != 3 or tuple(rows_first(hist).shape[1:]) != (d, n)
+                or hist.dtype != torch.float64 or hist.device != x.device or rows_first(hist).shape[0] > 1):
+            raise ValueError("hist must be a float64 tensor of at most one row shaped like the rows of x, on the device of x")
+        h = int(rows_first(hist).shape[0])
+    counts = _accumulator("counts", counts, (M, P + (1 if steps else 0), B), x, dtype=torch.int64)
+    if R == 0 or n == 0:
+        return counts
+    ring = torch.cat([rows_first(x), rows_first(hist)]) if h else rows_first(x).contiguous()   # the row before row 0 of a ring is its last
+    _marginals_fold(ring, 0, R, h, m, dirs, B, steps, counts)
+    return counts
+
+
+def _marginals_fold(ring, first_row, n_rows, n_hist, m, dirs, bins, steps, counts):
+    """gsss_target_marginals on the rows first_row .. + n_rows of a contiguous ring (rows, d, n)."""
+    rows, d, n = (int(v) for v in ring.shape)
+    dev = _device_index(ring)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsss_target_marginals(ring.data_ptr(), rows, first_row, n_rows, n_hist, n, d, m, dirs.data_ptr(),
+                                                     int(dirs.shape[1]), bins, _lib.MARGINALS_STEP if steps else 0,
+                                                     counts.data_ptr(), dev, current_stream_ptr(dev)))
+
+
+def marginal_quantile(counts, edges, q):
+    """Quantiles of histograms: counts (..., B) over the B equal bins between edges (B + 1,), q one level or several in [0, 1] ->
+    (...,) or (..., Q).  With N the sum of a row, cum its running count and width = (edges[B] - edges[0]) / B: b is the first
+    bin with cum_b >= q N (the first non-empty one for q = 0) and the value edges[b] + width (q N - cum_{b-1}) / count_b -- the
+    draws of a bin taken as spread evenly over it.  NaN for an empty row.  CPU or CUDA tensors."""
+    c = _t(counts).to(torch.float64)
+    e = _t(edges).to(c)
+    B = int(c.shape[-1])
+    if c.ndim < 1 or B < 1 or tuple(e.shape) != (B + 1,):
+        raise ValueError("counts must be (..., B) and edges (B + 1,)")
+    qs = torch.as_tensor(q, dtype=torch.float64, device=c.device)
+    if bool(((qs < 0) | (qs > 1)).any()):
+        raise ValueError("a quantile level lies in [0, 1]")
+    cum = torch.cumsum(c, -1)
+    total = cum[..., -1:]
+    want = total * qs.reshape(-1)                                                         # (..., Q)
+    first = torch.searchsorted(cum, torch.full_like(total, 0.5))                          # the first non-empty bin
+    b = torch.clamp(torch.maximum(torch.searchsorted(cum, want), first), max=B - 1)
+    before = torch.where(b > 0, torch.gather(cum, -1, torch.clamp(b - 1, min=0)), torch.zeros_like(want))
+    value = e[b] + (e[-1] - e[0]) / B * (want - before) / torch.gather(c, -1, b)
+    value = torch.where(total > 0, value, torch.full_like(value, float("nan")))
+    return value[..., 0] if qs.ndim == 0 else value
+
+
+def from_target_marginals(counts, n_dirs, *, steps=False):
+    """Per-target marginal densities and quantiles from the counts of `target_marginals` / `Sampler.summarize(marginals=)`:
+    counts (M, S, B), S = P + (1 if steps else 0), P = n_dirs.  With N the sum of a row and w the bin width:
+
+        marginal_edges (B + 1,) = linspace(-1, 1),  step_edges (B + 1,) = linspace(0, pi),
+        marginal_density (M, P, B) = counts / (N w): it integrates to 1 over [-1, 1]; NaN where the row is empty,
+        marginal_cdf (M, P, B) = running count / N, the value at every bin's upper edge,
+        marginal_quantiles (M, P, 5) at q = 0.025, 0.25, 0.5, 0.75, 0.975 and marginal_median (M, P) = the one at 0.5,
+
+    and with steps step_density (M, B) and step_quantiles (M, 5) of the geodesic step.  The quantile rule (`marginal_quantile`,
+    which takes any q): with cum the running count, b is the first bin with cum_b >= q N, the value
+    edge_b + w (q N - cum_{b-1}) / count_b.  CPU or CUDA tensors."""
+    c = _t(counts)
+    P, S = int(n_dirs), int(n_dirs) + (1 if steps else 0)
+    if c.ndim != 3 or P < 0 or c.shape[1] != S or c.shape[2] < 2:
+        raise ValueError(f"counts must be (M, {S}, B) for {P} directions{' and the steps' if steps else ''} (got {tuple(c.shape)})")
+    B = int(c.shape[2])
+    c = c.to(torch.float64)
+    edges = torch.from_numpy(np.linspace(-1.0, 1.0, B + 1)).to(c.device)
+    step_edges = torch.from_numpy(np.linspace(0.0, np.pi, B + 1)).to(c.device)
+    qs = list(MARGINAL_QUANTILES)
+
+    def density(rows, lo, hi):
+        return rows / (rows.sum(-1, keepdim=True) * ((hi - lo) / B))
+    u = c[:, :P]
+    quantiles = marginal_quantile(u, edges, qs)
+    out = {"marginal_edges": edges, "step_edges": step_edges, "marginal_density": density(u, -1.0, 1.0),
+           "marginal_cdf": torch.cumsum(u, -1) / u.sum(-1, keepdim=True), "marginal_quantiles": quantiles,
+           "marginal_median": quantiles[..., qs.index(0.5)]}
+    if steps:
+        out["step_density"] = density(c[:, P], 0.0, float(np.pi))
+        out["step_quantiles"] = marginal_quantile(c[:, P], step_edges, qs)
+    return out
+
+
 LADDER_SLOTS = 10  # doubles per pair-chain of gsss_batch_ladder
 
 
@@ -812,7 +979,14 @@ class TargetMoments:
     `ladder` = R, `ladder_acc` (G, R - 1, m, 10) (see `target_ladder`), from which into= goes on, and `ladder_hot_log_z` (G,), the
     batch's `hot_log_z` (NaN where the hottest rung is not flat).  stats() then adds log_z_ratio (the forward estimate; the
     backward one is reported beside it as a check, not averaged in), log_z_ratio_forward, log_z_ratio_backward, log_z_lower,
-    log_z_upper, log_z_ratio_se, used, skipped, log_z and hot_log_z (`from_target_ladder`)."""
+    log_z_upper, log_z_ratio_se, used, skipped, log_z and hot_log_z (`from_target_ladder`).
+
+    With `summarize(marginals=)` also the marginal histograms of every target along its own directions: `marg_counts` (M, S, B)
+    int64 (see `target_marginals`), the directions `marg_dirs` (M, P, d), `marg_bins` = B and `marg_steps`, whether series P
+    counts the geodesic steps, from which into= goes on; with the steps and without lags `hist` is the one last retained row, so
+    that the pair at the seam of two calls counts exactly once.  stats() then adds marginal_edges, step_edges, marginal_density,
+    marginal_cdf, marginal_quantiles, marginal_median and, with the steps, step_density and step_quantiles
+    (`from_target_marginals`); `quantile(q)` gives the marginals' quantiles at any level."""
 
     def __init__(self, acc, chain_sum, d, chains_per_target, second_moment, lp_acc=None, lp_chain_sum=None, lp_best=None,
                  x_best=None):
@@ -823,12 +997,14 @@ class TargetMoments:
         self.mix_step, self.mix_counts, self.mix_modes, self.mix_weights = None, None, None, None
         self.mix_dirs, self.mix_transitions = None, False
         self.ladder, self.ladder_acc, self._ladder_hot, self._ladder_source = None, None, None, None
+        self.marg_counts, self.marg_dirs, self.marg_bins, self.marg_steps = None, None, None, False
 
     @classmethod
     def begin(cls, n, d, chains_per_target, device, *, second_moment=None, log_prob=False, lags=None, mixing=None, ladder=None,
-              ladder_source=None):
+              ladder_source=None, marginals=None):
         """Zeroed accumulators of n chains in d dimensions on `device` and of the features asked for: log_prob, lags = L, mixing =
-        dict(hop, modes, weights, transitions), ladder = R with ladder_source = (batch, first ladder) for `ladder_hot_log_z`."""
+        dict(hop, modes, weights, transitions), ladder = R with ladder_source = (batch, first ladder) for `ladder_hot_log_z`,
+        marginals = dict(bins, directions, steps)."""
         m = int(chains_per_target)
         M = n // m
         full, rows = _moments_form(d, second_moment)
@@ -858,9 +1034,15 @@ class TargetMoments:
         if ladder is not None:
             tm.ladder, tm._ladder_source = ladder, ladder_source
             tm.ladder_acc = zeros(M // ladder, ladder - 1, m, LADDER_SLOTS)
+        if marginals is not None:
+            tm.marg_dirs, P = _marginal_dirs(marginals["directions"], M, d, device)
+            tm.marg_steps = bool(marginals["steps"])
+            tm.marg_bins = _marginal_shape(marginals["bins"], P, tm.marg_steps)
+            tm.marg_counts = zeros(M, P + (1 if tm.marg_steps else 0), tm.marg_bins, dtype=torch.int64)
         return tm
 
-    def check_continues(self, n, d, chains_per_target, *, second_moment=None, log_prob=False, lags=None, mixing=None, ladder=None):
+    def check_continues(self, n, d, chains_per_target, *, second_moment=None, log_prob=False, lags=None, mixing=None, ladder=None,
+                        marginals=None):
         """ValueError unless into= can go on with this call: the same chains and form, and no feature it was begun without."""
         full, rows = _moments_form(d, self.second_moment if second_moment is None else second_moment)
         M = n // chains_per_target
@@ -878,6 +1060,11 @@ class TargetMoments:
         if ladder is not None and self.ladder != ladder:
             raise ValueError("into= was begun without log_z along these ladders: the ratios of its draws so far were not kept, so "
                              "it cannot take them up")
+        if marginals is not None and (self.marg_counts is None or self.marg_bins != int(marginals["bins"])
+                                      or int(self.marg_dirs.shape[1]) != _n_marginal_dirs(marginals["directions"], d)
+                                      or self.marg_steps != bool(marginals["steps"])):
+            raise ValueError("into= was begun without these marginals (bins, number of directions, steps): the histograms of its "
+                             "draws so far were not kept, so it cannot take them up")
 
     @property
     def n_targets(self):
@@ -886,7 +1073,7 @@ class TargetMoments:
     @property
     def hist_rows(self):
         """Rows of history the ring of `summarize` keeps before a window: the lags, one at least for the pair of a step."""
-        return max(self.lags or 0, 1) if self.mix_step is not None else self.lags or 0
+        return max(self.lags or 0, 1) if self.mix_step is not None or self.marg_steps else self.lags or 0
 
     @property
     def hist_seen(self):
@@ -927,6 +1114,8 @@ class TargetMoments:
         if self.mix_step is not None:
             _mixing_fold(ring, first, n_rows, min(1, n_hist), m, self.mix_dirs, self.mix_modes, self.mix_transitions, self.mix_step,
                          self.mix_counts)
+        if self.marg_counts is not None:
+            _marginals_fold(ring, first, n_rows, min(1, n_hist), m, self.marg_dirs, self.marg_bins, self.marg_steps, self.marg_counts)
         if self.ladder is not None:
             lib, handle, target0 = batch
             _ladder_fold(handle, lib, x.contiguous(), n_rows, n, target0, self.ladder, scratch, self.ladder_acc)
@@ -966,7 +1155,17 @@ class TargetMoments:
         if self.ladder_acc is not None:
             out.update(from_target_ladder(self.ladder_acc, hot_log_z=self.ladder_hot_log_z))
             out["hot_log_z"] = torch.as_tensor(self.ladder_hot_log_z, dtype=torch.float64).to(self.ladder_acc.device)
+        if self.marg_counts is not None:
+            out.update(from_target_marginals(self.marg_counts, int(self.marg_dirs.shape[1]), steps=self.marg_steps))
         return out
+
+    def quantile(self, q):
+        """The quantiles of every target's marginals at the level(s) q in [0, 1]: (M, P) or (M, P, Q) (`marginal_quantile`)."""
+        if self.marg_counts is None:
+            raise ValueError("this summary was begun without marginals: summarize(marginals=...) keeps the histograms")
+        P = int(self.marg_dirs.shape[1])
+        edges = torch.from_numpy(np.linspace(-1.0, 1.0, self.marg_bins + 1)).to(self.marg_counts.device)
+        return marginal_quantile(self.marg_counts[:, :P], edges, q)
 
 
 def _average_ranks(flat):

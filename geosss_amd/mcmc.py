@@ -813,7 +813,7 @@ class RejectionSphericalSliceSampler:
         return out[0] if self._single else out
 
     def summarize(self, n_samples, burnin=0, *, thin=1, window=None, second_moment=None, chains_per_target=None, into=None,
-                  log_prob=False, lags=None, mixing=False, exchange=None, log_z=False):
+                  log_prob=False, lags=None, mixing=False, exchange=None, log_z=False, marginals=False):
         """Per-target posterior moments and R-hat of a run without storing it: the draws `sample(n_samples, burnin, thin=thin)`
         would return -- the state after `burnin` transitions is draw 0, n_samples - 1 thinned draws follow -- are written in
         windows of `window` retained rows into ONE reused buffer in the kernels' component-major layout, and every window is
@@ -866,6 +866,18 @@ class RejectionSphericalSliceSampler:
         way.  into= continues the sums; a summary begun without log_z cannot take it up.  The moments, the chains and the
         other launches are untouched by it.
 
+        marginals=True or marginals=dict(bins=, directions=, steps=) (any sampler, batch or single target, beside every other
+        feature): also the SHAPE of every posterior, which no sum gives -- per target the histogram of u = x . v over `bins`
+        (2 .. 1024, default 64) equal bins of [-1, 1] along each of its directions v, from which stats() reports densities,
+        CDFs, medians, quartiles and 95 % intervals and `TargetMoments.quantile(q)` any other level.  directions: (P, d) for
+        every target or (M, P, d) for the M targets of this sampler, P <= 32, unit vectors or not (None: the d coordinate axes;
+        True is dict(bins=64, directions=None, steps=False)).  steps=True adds the histogram of the geodesic step between
+        consecutive retained draws over [0, pi]; the buffer then becomes a ring with at least one row of history, as with
+        mixing=.  Every window is folded by gsss_target_marginals beside the other folds, integer counts alone, so the same
+        retained rows give the same counts however they are cut into windows and calls.  into= continues the counts with the directions they were
+        begun with; a summary begun without them, or with other bins, another number of directions or without the steps,
+        cannot take them up.  The moments, the chains and the other launches are untouched by it.
+
         What each feature keeps on the result and what stats() reports for it: `diagnostics.TargetMoments`.  Where the windows
         lie in the buffer: `diagnostics.ring_plan`."""
         if exchange is not None:
@@ -874,7 +886,7 @@ class RejectionSphericalSliceSampler:
             with self._exchanging(exchange):
                 return self.summarize(n_samples, burnin, thin=thin, window=window, second_moment=second_moment,
                                       chains_per_target=chains_per_target, into=into, log_prob=log_prob, lags=lags, mixing=mixing,
-                                      log_z=log_z)
+                                      log_z=log_z, marginals=marginals)
         from . import diagnostics
         if not n_samples > 0:
             raise AssertionError("n_samples must be positive")
@@ -891,7 +903,8 @@ class RejectionSphericalSliceSampler:
         if log_prob and self._batch_m is None:
             raise ValueError("summarize(log_prob=True) evaluates the draws with the batch kernel: wrap the target in a TargetBatch "
                              "of one (TargetBatch([pdf]), chains_per_target = n_chains)")
-        asked = {"second_moment": second_moment, "log_prob": bool(log_prob), "lags": lags, "mixing": None, "ladder": None}
+        asked = {"second_moment": second_moment, "log_prob": bool(log_prob), "lags": lags, "mixing": None, "ladder": None,
+                 "marginals": None}
         if log_z is not None and log_z is not False:
             asked["ladder"] = self._ladder_plan(log_z, self._exchange_active[0] if self._exchange_active else None)
         if lags is not None:
@@ -902,6 +915,8 @@ class RejectionSphericalSliceSampler:
                                  f"lags = {lags})")
         if mixing is not None and mixing is not False:
             asked["mixing"] = self._mixing_plan(mixing)
+        if marginals is not None and marginals is not False:
+            asked["marginals"] = diagnostics._marginals_plan(marginals)
         if into is None:
             tm = diagnostics.TargetMoments.begin(n, d, m, self._tdev, **asked,
                                                  ladder_source=(self.target, self.chain_offset // m // (asked["ladder"] or 1)))

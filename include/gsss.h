@@ -443,6 +443,39 @@ int gsss_target_mixing(const double *ring_dev, int64_t ring_rows, int64_t first_
                        int64_t n_chains, int32_t d, int64_t chains_per_target, const double *dirs_dev, int32_t n_modes,
                        int32_t flags, double *step_dev, int64_t *count_dev, int device, void *stream);
 
+/* Per-TARGET marginal histograms of retained draws, streamed: the shape of every posterior of a batch -- the histogram of u^T x
+ * the reference draws for the Bingham experiment (scripts/Bingham.ipynb), the coordinate marginals of scripts/vMF_diagnostics.py
+ * and curve_3d.py::marginal_distribution_plot, the histogram of geodesic steps of curve_3d.py::geodesic_distance_plot -- for
+ * ensembles in which target t owns the chains [t m, (t + 1) m), m = chains_per_target, and EVERY TARGET HAS ITS OWN DIRECTIONS, by
+ * a kernel of its own beside the sampler, so it serves every kernel family, mode and dimension.  ring_dev is component-major
+ * [ring_rows][d][n_chains] with the block semantics of gsss_target_mixing: the block is the rows first_row .. first_row + n_rows
+ * - 1 (it does not wrap); with n_hist = 1 the draw that precedes it is the row (first_row - 1) mod ring_rows, read where it lies.
+ * A pair (r, r - 1) counts in the call whose block holds r.  The history serves the step series alone: without
+ * GSSS_MARGINALS_STEP n_hist = 1 is accepted and ignored, the row is not read.
+ * dirs_dev [n_chains / m][n_dirs][d], per target t its P = n_dirs directions v_{t,p} (P = 0 .. 32); they need not be unit vectors.
+ * count_dev [n_chains / m][S][n_bins], int64, ADDED to, S = gsss_marginal_rows / n_bins = P + (GSSS_MARGINALS_STEP ? 1 : 0), B = n_bins:
+ *     series p < P     per draw of the target: u = sum_j x_j v_{t,p,j}, a chain of fused multiply-adds in component order from
+ *                      0.0 (the arithmetic of gsss_target_mixing's x . h); t = (u + 1.0) * (0.5 * B); bin 0 if t < 0, else
+ *                      min(B - 1, (int)t): B equal bins over [-1, 1], what lies outside counted in the first and the last
+ *     series P         with GSSS_MARGINALS_STEP, per pair: theta = acos(fmin(fmax(dot, -1), 1)), dot = x_r . x_{r-1} the chain of
+ *                      fused multiply-adds of gsss_target_mixing; t = theta * scale, scale = (double)B / M_PI formed once on
+ *                      the host; bin min(B - 1, (int)t): B equal bins over [0, pi]
+ * A NaN u is counted in no bin, nor is the step of a pair whose dot is NaN (the clamp would turn it into pi).
+ * No floating-point sums are kept.  The counters are integers added with integer atomics -- 32-bit in LDS, then one 64-bit add
+ * to count_dev per non-zero counter of a workgroup --: the same result in any order, and successive calls over successive blocks
+ * of a series give the counts of the whole series.
+ * GSSS_E_INVALID: d < 2, m < 1, n_chains no multiple of m, a negative count, first_row + n_rows > ring_rows, n_hist > 1 or
+ * > ring_rows - n_rows, n_dirs < 0, n_dirs = 0 without GSSS_MARGINALS_STEP, n_bins < 2, unknown flags, a NULL ring_dev / count_dev
+ * (dirs_dev with n_dirs > 0) with a non-empty block; GSSS_E_UNSUPPORTED: n_dirs > 32, n_bins > 1024, S n_bins > 8192 (32 KB of
+ * 32-bit LDS counters per target; gsss_marginal_rows returns the same codes for the three arguments it takes), n_rows > 2^23 (a
+ * workgroup's 32-bit counter takes 256 lanes x 2^23 rows) -- all of them before the device is touched.  n_rows = 0 does nothing.
+ * The reference takes np.histogram of one stored chain on the host. */
+#define GSSS_MARGINALS_STEP 1
+int64_t gsss_marginal_rows(int32_t n_dirs, int32_t n_bins, int32_t flags);
+int gsss_target_marginals(const double *ring_dev, int64_t ring_rows, int64_t first_row, int64_t n_rows, int64_t n_hist,
+                          int64_t n_chains, int32_t d, int64_t chains_per_target, const double *dirs_dev, int32_t n_dirs,
+                          int32_t n_bins, int32_t flags, int64_t *count_dev, int device, void *stream);
+
 /* Replica exchange (parallel tempering) along ladders of members of a gsss_target_create_batch handle: ONE sweep of one parity
  * over the chains of a launch.  state_dev is component-major [d][n_chains], chain 0 being the first chain of member `target0`;
  * m = the handle's chains_per_target.  The n_chains / m members form ladders of `ladder` consecutive members; a sweep of parity p
